@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X Guetzli search path (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(metric, value, ms_per_step, the workload and the timed region's host
+figures).  --dump-outputs DIR also writes what the last timed step returned
+(see dump_outputs).  --full adds every other leg described below: the
+known-answer check, the isolated frame with its rooflines, the 4K and
+8192x8192 legs and the CPU baseline.
 
 A step is the end-to-end `guetzli::Process` encode of a batch of
 --frames-per-step synthetic sRGB frames per GPU (each frame is BASELINE.json
@@ -14,14 +21,16 @@ every rank encodes its own frames (image-level sharding, no data-path
 collective) and the JPEG byte strings are gathered to rank 0 over RCCL at
 the end of each step.  value = total pixels of all ranks / max-over-ranks
 wall time.  `--gpus N` without a torch.distributed.run environment starts
-the N ranks itself (one process per GPU, before any HIP call).
+the N ranks itself (one process per GPU, before any HIP call).  The first
+16 steps (warm-up included) encode frames of their own; a longer run goes
+round those frames again, so its set-up time does not grow with --steps.
 
 The first timed step of every rank encodes the synthetic frames whose
 reference (`guetzli --c`) bytes are committed (tests/golden/manifest.json,
-1080p q95 seeds 0..7); they are checked after the timed region ("verified"),
-and a mismatch fails the run.
+1080p q95 seeds 0..7); with --full they are checked after the timed region
+("verified"), and a mismatch fails the run.
 
-Also reported (one JSON line on rank 0):
+Also reported with --full (one JSON line on rank 0):
   single_frame  one frame encoded alone after the timed region (latency).
   roofline      north_star's: the Butteraugli blur+mask pass at 4K against
                 HBM -- one BASELINE configs[2] frame (3840x2160 q90, seed 0,
@@ -634,6 +643,40 @@ def north_star_roofline(uhd):
                 "bytes verified" if uhd["bit_exact"] else "BYTES NOT VERIFIED")}
 
 
+# Steps with input frames of their own (warm-up included; the default run's
+# 1 + 8 steps are all distinct); later steps reuse them in order.
+DISTINCT_STEPS = 16
+
+# --dump-outputs: at most this many array bytes per run (all ranks' files).
+DUMP_BUDGET_BYTES = 48 << 20
+
+
+def dump_outputs(path, jpegs, stats, rank, world):
+    """--dump-outputs DIR: what the last timed step returned to its caller,
+    per frame the JPEG byte string and the search's iteration count, as
+    float32 / float64 .npy files (the frames of that step depend on the
+    arguments alone, so two builds can be compared file by file):
+      jpeg_<f>.npy      the frame's JPEG bytes, one float32 per byte; of a
+                        string over the per-frame share of the budget, the
+                        bytes at a fixed seeded sample of positions (sorted)
+      jpeg_bytes.npy    float64, the frames' JPEG lengths
+      iterations.npy    float64, the frames' search iterations
+    Ranks above 0 of a multi-GPU run write <name>_rank<r>.npy."""
+    os.makedirs(path, exist_ok=True)
+    tag = "" if rank == 0 else "_rank%d" % rank
+    share = DUMP_BUDGET_BYTES // (4 * max(1, world * len(jpegs)))
+    for f, data in enumerate(jpegs):
+        a = np.frombuffer(data, np.uint8)
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(f).choice(a.size, share, replace=False))
+            a = a[idx]
+        np.save(os.path.join(path, "jpeg_%d%s.npy" % (f, tag)), a.astype(np.float32))
+    np.save(os.path.join(path, "jpeg_bytes%s.npy" % tag),
+            np.array([len(d) for d in jpegs], np.float64))
+    np.save(os.path.join(path, "iterations%s.npy" % tag),
+            np.array([st.iterations for st in stats], np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -655,14 +698,22 @@ def main():
                     help="start a step's frames only after the previous step's last frame "
                          "finished (default: the timed steps' frames go through one queue, "
                          "--in-flight at a time, so a frame starts when any frame finishes)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (JPEG bytes and "
+                         "iteration counts per frame) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also: check the known-answer frames against the "
+                         "reference's bytes, encode one frame alone (latency, per-kernel times, "
+                         "rooflines), the 4K and 8192x8192 legs and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-baseline-processes", type=int, default=8)
     ap.add_argument("--no-large-frame", action="store_true",
-                    help="skip the BASELINE configs[4] leg (8192x8192 q84: one engine at N < 4, "
-                         "4 row strips over GPUs 0-3 at N >= 4)")
+                    help="with --full: skip the BASELINE configs[4] leg (8192x8192 q84: one engine "
+                         "at N < 4, 4 row strips over GPUs 0-3 at N >= 4)")
     ap.add_argument("--no-uhd-frame", action="store_true",
-                    help="skip the BASELINE configs[2] leg (one 3840x2160 q90 frame encoded alone "
-                         "after the timed region: the north_star blur+mask roofline at 4K)")
+                    help="with --full: skip the BASELINE configs[2] leg (one 3840x2160 q90 frame "
+                         "encoded alone after the timed region: the north_star blur+mask roofline "
+                         "at 4K)")
     ap.add_argument("--dist-selftest", action="store_true",
                     help="CPU check of the multi-rank path (launcher, gloo, byte gather, "
                          "max-over-ranks timing) with stand-in payloads; no GPU")
@@ -690,18 +741,28 @@ def main():
     # distinct frames per (rank, step, slot), uploaded to HBM before timing;
     # the first timed step of every rank is the known-answer frames (seeds
     # 0..) where the manifest has them
+    # Generating a frame costs the host far more than encoding it costs the
+    # GPU, so the first DISTINCT_STEPS steps (warm-up included) get frames of
+    # their own and a longer run goes round them again (step s encodes the
+    # frames of step s % DISTINCT_STEPS), and the frames are generated on the
+    # usable cores at once: set-up stays bounded whatever --steps is.
     kn = known_answers(w, h, q)
+    nslots = max(1, min(nsteps, DISTINCT_STEPS))
     seeds = []
-    for s in range(nsteps):
+    for s in range(nslots):
         row = []
         for f in range(args.frames_per_step):
-            if s == args.warmup and f in kn:
+            if s == args.warmup % nslots and f in kn:
                 row.append(f)
             else:
                 row.append(1000 + rank * 100000 + s * 100 + f)
         seeds.append(row)
-    frames = [[torch.from_numpy(gz.synthetic_frame(sd, w, h).reshape(-1)).to(f"cuda:{dev}")
-               for sd in row] for row in seeds]
+    with concurrent.futures.ThreadPoolExecutor(
+            max_workers=max(1, min(16, len(os.sched_getaffinity(0))))) as gen:
+        rows = [gen.map(lambda sd: gz.synthetic_frame(sd, w, h), row) for row in seeds]
+        slots = [[torch.from_numpy(a.reshape(-1)).to(f"cuda:{dev}") for a in row] for row in rows]
+    frames = [slots[s % nslots] for s in range(nsteps)]
+    seeds = [seeds[s % nslots] for s in range(nsteps)]
     torch.cuda.synchronize()
 
     in_flight = args.in_flight if args.in_flight > 0 else args.frames_per_step
@@ -734,6 +795,7 @@ def main():
     iters = []
     conc = {}
     checked = []
+    last = ([], [])
     keys = ("seconds_total", "seconds_setup", "seconds_write", "seconds_quantize",
             "seconds_backend", "seconds_compare", "seconds_zeroing")
     # Streaming (default): every timed frame is queued at once and the pool
@@ -743,7 +805,7 @@ def main():
     # done.  --lockstep: a step starts when the previous one has finished.
     futs = {} if args.lockstep else {s: submit(s) for s in range(args.warmup, nsteps)}
     for s in range(args.warmup, nsteps):
-        out, stats = step(s, futs.get(s))
+        out, stats = step(s, futs.pop(s, None))  # (a finished step's bytes are not kept)
         if s == args.warmup:
             checked = [(seeds[s][f], out[f], stats[f].iterations)
                        for f in range(len(out)) if seeds[s][f] in kn]
@@ -751,6 +813,7 @@ def main():
         for st in stats:
             for k in keys:
                 conc[k] = conc.get(k, 0.0) + getattr(st, k) / (args.steps * len(stats))
+        last = (out, stats)
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
@@ -764,40 +827,41 @@ def main():
         print("thread cpu:", [(round(c, 3), n) for c, n in rows[:24] if c > 0.001], file=sys.stderr)
     cpu_s = (ru1.ru_utime - ru0.ru_utime) + (ru1.ru_stime - ru0.ru_stime)
     cpu_per_frame = cpu_s / (args.steps * args.frames_per_step)
-    # verification of the known-answer frames (after the timed region)
-    ok = sum(1 for sd, data, it in checked
-             if (hashlib.sha256(data).hexdigest(), it) == kn[sd])
-    counts = [len(checked), ok]
+    # --full: verification of the known-answer frames (after the timed region)
+    counts = [0, 0]
+    if args.full:
+        ok = sum(1 for sd, data, it in checked
+                 if (hashlib.sha256(data).hexdigest(), it) == kn[sd])
+        counts = [len(checked), ok]
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-        c = torch.tensor(counts, dtype=torch.int64, device=cdev)
-        dist.all_reduce(c, op=dist.ReduceOp.SUM)
-        counts = [int(v) for v in c.tolist()]
+        if args.full:
+            c = torch.tensor(counts, dtype=torch.int64, device=cdev)
+            dist.all_reduce(c, op=dist.ReduceOp.SUM)
+            counts = [int(v) for v in c.tolist()]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last[0], last[1], rank, world)
 
-    # isolated frame: latency, host breakdown and per-kernel HIP-event timing
-    gz.profile_reset()
-    gz.profile_enable(True)
-    t1 = time.perf_counter()
-    _, st1 = encode(frames[0][0])
-    single_s = time.perf_counter() - t1
-    gz.profile_enable(False)
-    prof = gz.profile_read()
-    host = {}
-    for k in keys:
-        host[k] = getattr(st1, k)
-    host.update(gz.last_process_detail())
+    if args.full:
+        # isolated frame: latency, host breakdown and per-kernel HIP-event timing
+        gz.profile_reset()
+        gz.profile_enable(True)
+        t1 = time.perf_counter()
+        _, st1 = encode(frames[0][0])
+        single_s = time.perf_counter() - t1
+        gz.profile_enable(False)
+        prof = gz.profile_read()
+        host = {}
+        for k in keys:
+            host[k] = getattr(st1, k)
+        host.update(gz.last_process_detail())
 
     out = None
     if rank == 0:
         total_px = world * args.steps * args.frames_per_step * w * h
         value = total_px / elapsed / 1e6
-
-        rep = frame_report(prof, w, h, int(host.get("candidates", 0)))
-        regions = rep["regions"]
-        uhd = None if args.no_uhd_frame else uhd_frame(gz, dev)
-        gpu_frame_ms = sum(ms for ms, _, _ in regions)
 
         out = {
             "metric": METRIC,
@@ -824,6 +888,19 @@ def main():
                        "parallelism": "image-sharded over %d GPU(s)%s" % (
                            world, ", RCCL all_gather of JPEG bytes" if world > 1 else ""),
                        "search_iterations": iters},
+            "concurrent_frame_breakdown_seconds": {k: round(v, 4) for k, v in conc.items()},
+            "host_cpu_seconds_per_frame": round(cpu_per_frame, 4),
+            "host_cores_busy_per_gpu": round(cpu_s / elapsed, 2),
+            "host_cpu_user_system_seconds_per_frame": [
+                round((ru1.ru_utime - ru0.ru_utime) / (args.steps * args.frames_per_step), 4),
+                round((ru1.ru_stime - ru0.ru_stime) / (args.steps * args.frames_per_step), 4)],
+        }
+    if rank == 0 and args.full:
+        rep = frame_report(prof, w, h, int(host.get("candidates", 0)))
+        regions = rep["regions"]
+        uhd = None if args.no_uhd_frame else uhd_frame(gz, dev)
+        gpu_frame_ms = sum(ms for ms, _, _ in regions)
+        out.update({
             "verified": {"frames": counts[0], "bit_exact": counts[1],
                          "against": "reference guetzli --c sha256 + iterations "
                                     "(tests/golden/manifest.json)"},
@@ -835,22 +912,16 @@ def main():
             "stages": rep["stages"],
             "gpu_ms_per_frame_isolated": round(gpu_frame_ms, 3),
             "gpu_regions_ms_per_frame": {n: round(ms, 4) for ms, n, _ in regions},
-            "concurrent_frame_breakdown_seconds": {k: round(v, 4) for k, v in conc.items()},
-            "host_cpu_seconds_per_frame": round(cpu_per_frame, 4),
-            "host_cores_busy_per_gpu": round(cpu_s / elapsed, 2),
-            "host_cpu_user_system_seconds_per_frame": [
-                round((ru1.ru_utime - ru0.ru_utime) / (args.steps * args.frames_per_step), 4),
-                round((ru1.ru_stime - ru0.ru_stime) / (args.steps * args.frames_per_step), 4)],
             "single_frame": {"seconds": round(single_s, 4),
                              "Mpixels_per_s": round(w * h / single_s / 1e6, 4),
                              "iterations": st1.iterations,
                              "host_breakdown_seconds": {k: round(v, 4) for k, v in host.items()}},
-        }
+        })
         if uhd is not None:
             out["configs2_4k"] = uhd
             out["blur_mask_pass_4k"] = uhd["blur_mask_pass"]
     large = None
-    if not args.no_large_frame:
+    if args.full and not args.no_large_frame:
         # (a side leg after the timed region: a failure there is reported in
         # the line instead of losing it; with N >= 4 its strip ranks exchange
         # through collectives, and a watchdog prints the line without the leg
@@ -888,7 +959,7 @@ def main():
         return
     if large is not None:
         out["configs4_8192"] = large
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline(w, h, q, args.cpu_baseline_processes)
     print(json.dumps(out), flush=True)
     pool.shutdown()

@@ -32,7 +32,7 @@ export TMPDIR=/tmp
 O=$ROOT/gpurun_out/${GZ_AB_OUT:-ab}
 mkdir -p "$O"
 MODE=${GZ_AB_MODE:-bench}
-SIDE="--no-cpu-baseline --no-large-frame --no-uhd-frame"
+SIDE="--full --no-cpu-baseline --no-large-frame --no-uhd-frame"
 case $MODE in
   bench) ARGS="--steps ${GZ_AB_STEPS:-4} --warmup 1 $SIDE"; RUNS=${GZ_AB_RUNS:-2} ;;
   frame) read -r W H Q <<< "${GZ_AB_SIZE:-1920 1080 95}"

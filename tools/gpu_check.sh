@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 timeout -k 10 500 python -u -m pytest -x -q --timeout 300 --timeout-method thread tests -m gpu > $O/tests.log 2>&1 || { tail -30 $O/tests.log; exit 1; }
 tail -1 $O/tests.log
 for i in 1 2; do
-  timeout -k 10 200 python bench.py --steps 6 --warmup 1 --no-cpu-baseline --no-large-frame --no-uhd-frame \
+  timeout -k 10 200 python bench.py --full --steps 6 --warmup 1 --no-cpu-baseline --no-large-frame --no-uhd-frame \
     > $O/bench$i.json 2> $O/bench$i.err || { tail $O/bench$i.err; exit 1; }
   python -c "import json; d=json.loads(open('$O/bench$i.json').read().strip().splitlines()[-1]); print('bench', d['value'], d['ms_per_step'], d['host_cpu_seconds_per_frame'], d['host_cores_busy_per_gpu'], d['verified']['bit_exact'])"
 done

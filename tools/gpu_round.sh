@@ -18,7 +18,7 @@ if [ -z "$GZ_SKIP_TESTS" ]; then
   tail -1 $O/smoke.log
 fi
 if [ -z "$GZ_SKIP_BENCH" ]; then
-  timeout -k 10 900 python bench.py > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
+  timeout -k 10 900 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
   head -c 300 $O/bench.json; echo
 fi
 timeout -k 10 120 rocprofv3 -L > $O/counters.txt 2>&1 || { tail -5 $O/counters.txt; exit 1; }
@@ -35,7 +35,7 @@ for sz in ${GZ_SIZES:-1920x1080x95 3840x2160x90}; do
   IFS=x read -r W H Q <<< "$sz"
   P=$O/prof_${W}x${H}
   rm -rf $P; mkdir -p $P
-  BARGS="--steps 1 --warmup 1 --frames-per-step 1 --no-cpu-baseline --no-large-frame --no-uhd-frame --width $W --height $H --quality $Q"
+  BARGS="--full --steps 1 --warmup 1 --frames-per-step 1 --no-cpu-baseline --no-large-frame --no-uhd-frame --width $W --height $H --quality $Q"
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $P/trace -o run --output-format csv \
     -- python bench.py $BARGS > $P/bench.json 2> $P/trace.err || { tail -5 $P/trace.err; exit 1; }
   echo "trace ${W}x${H} ok"
