@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "host/host_util.h"
 #include "host/jpeg_encode.h"
 #include "host/thread_pool.h"
 #include "../../include/guetzli_hip.h"
@@ -13,10 +14,6 @@
 namespace gz {
 
 namespace {
-using Clock = std::chrono::steady_clock;
-inline double Since(Clock::time_point t0) {
-  return std::chrono::duration<double>(Clock::now() - t0).count();
-}
 inline int BitLength(int v) { return v ? 32 - __builtin_clz(static_cast<uint32_t>(v)) : 0; }
 
 int CountFfBytes(uint32_t memory_order_word, int nbytes) {
@@ -548,7 +545,7 @@ bool PartitionComparator::Agree(bool ok, const std::string& local_err) {
 }
 
 bool StripDeviceOrder() {
-  static const bool host = getenv("GZ_STRIP_HOST_ORDER") && atoi(getenv("GZ_STRIP_HOST_ORDER")) != 0;
+  static const bool host = EnvFlag("GZ_STRIP_HOST_ORDER");
   return !host;
 }
 
@@ -900,7 +897,7 @@ int ProcessStrips(int device, const ProcessParams& params, const uint8_t* rgb, i
   // order, known-histogram coding and skipped scans; the strip machinery at
   // world 1 took 1.28 s for configs[4] against the engine's 1.14).
   // GZ_STRIP_FORCE=1 keeps the strip machinery, for its tests.
-  static const bool force = getenv("GZ_STRIP_FORCE") && atoi(getenv("GZ_STRIP_FORCE")) != 0;
+  static const bool force = EnvFlag("GZ_STRIP_FORCE");
   if (coll->world() == 1 && !force) {
     const int rc = Process(device, params, rgb, false, w, h, result, err);
     result->detail["strip_single_engine"] = 1;

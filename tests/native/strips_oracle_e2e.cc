@@ -135,7 +135,7 @@ int main(int argc, char** argv) {
   fwrite(out[0].data(), 1, out[0].size(), o);
   fclose(o);
   // (the back end's iterations whose order came from the ranks' own entries
-  // alone, and those that fell back to the exact order: host/processor.cc
+  // alone, and those that fell back to the exact order: host/backend.cc
   // StripOrder)
   printf("{\"bytes\": %zu, \"iters\": %d, \"world\": %d, \"strip_order_fast_iters\": %d, "
          "\"strip_order_fallbacks\": %d}\n",

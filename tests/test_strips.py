@@ -94,7 +94,7 @@ def test_oracle_strip_equals_full_image_on_owned_rows(gz, w, h, world, seed):
         assert np.array_equal(dc[:, y0 - e0:y1 - e0], full_dc[:, y0:y1])
 
 
-# The back end's order on a split frame (host/processor.cc StripOrder):
+# The back end's order on a split frame (host/backend.cc StripOrder):
 # from the ranks' own entries (default; tiny merge windows), every iteration
 # exact (the whole frame's entries on every rank), and the switch to the
 # exact order forced at the prefix / in mid-tail.
@@ -187,10 +187,11 @@ def test_torch_collectives_gloo_world2():
     assert res == {0: "ok", 1: "ok"}
 
 
-def _gpu_strip_rank(rank, world, port, e, q, force=False):
+def _gpu_strip_rank(rank, world, port, e, q, force=False, env=None):
     import sys
     if force:  # (world 1 runs the strip machinery, not the single-engine search)
         os.environ["GZ_STRIP_FORCE"] = "1"
+    os.environ.update(env or {})  # (before the import: the knobs are read once per process)
     sys.path.insert(0, os.path.join(ROOT, "guetzli-cuda-opencl_amd", "python"))
     import torch.distributed as dist
     import guetzli_amd as gz
@@ -204,11 +205,33 @@ def _gpu_strip_rank(rank, world, port, e, q, force=False):
         coll = gz.Collectives.from_torch(dist, "cpu")
         data = gz.process_strips(rgb, e["w"], e["h"], coll, gz.Params.for_quality(e["quality"]),
                                  device=0)
-        q.put((rank, hashlib.sha256(data).hexdigest()))
+        q.put((rank, (hashlib.sha256(data).hexdigest(), gz.last_process_detail())))
     except Exception as ex:
-        q.put((rank, repr(ex)))
+        q.put((rank, (repr(ex), {})))
     finally:
         dist.destroy_process_group()
+
+
+def _run_gpu_strip_ranks(e, world, force=False, env=None, timeout=600):
+    """{rank: (sha256 or error, detail counters)} of `world` spawned ranks;
+    no rank outlives the call, whatever happens to it."""
+    import torch.multiprocessing as mp
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_gpu_strip_rank, args=(r, world, port, e, q, force, env)) for r in range(world)]
+    try:
+        for p in procs:
+            p.start()
+        res = dict(q.get(timeout=timeout) for _ in procs)
+        for p in procs:
+            p.join(60)
+        return res
+    finally:
+        for p in procs:
+            if p.is_alive():
+                p.kill()
+            p.join(10)
 
 
 @pytest.mark.gpu
@@ -222,18 +245,42 @@ def test_gpu_strips_reproduce_reference(name, world, force):
     BASELINE configs[4] (8192x8192 q84 as 4 strips of 2048 rows + halo).  One
     rank: the single-engine search by default, the strip machinery with
     GZ_STRIP_FORCE=1 (force)."""
-    import torch.multiprocessing as mp
     e = MANIFEST["e2e"].get(name) or MANIFEST["synthetic"][name]
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_gpu_strip_rank, args=(r, world, port, e, q, force)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = dict(q.get(timeout=600) for _ in procs)
-    for p in procs:
-        p.join(60)
-    assert len(res) == world and all(v == e["sha256"] for v in res.values()), res
+    res = _run_gpu_strip_ranks(e, world, force)
+    assert len(res) == world and all(v[0] == e["sha256"] for v in res.values()), \
+        {r: v[0] for r, v in res.items()}
+
+
+# Knobs that send a frame split over ranks through the back end's other
+# paths, and the counters (gz.last_process_detail) of which one must move on
+# rank 0, so that the forced path is known to have run.
+GPU_STRIP_VARIANTS = {
+    # every bulk prefix reported open: the frame's entries gathered on every
+    # rank, the owned blocks' prefix share applied on each rank's device
+    "select_open": ({"GZ_SELECT_OPEN": "1"}, ("backend_select_open",)),
+    # every selection's window overflows: no window at all, the tail goes
+    # straight to the exact order (the ranks' entries gathered)
+    "sel_overflow": ({"GZ_SEL_OVERFLOW": "1"}, ("strip_order_fallbacks",)),
+    # 16-entry windows run out: the next window, then the mid-tail switch
+    "tail_window16": ({"GZ_TAIL_WINDOW": "16"}, ("backend_tail_windows", "backend_tail_exact")),
+    # the host order (StripOrder) with the strips' engines on the GPU
+    "host_order": ({"GZ_STRIP_HOST_ORDER": "1"}, ("strip_order_fast_iters",)),
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant", sorted(GPU_STRIP_VARIANTS))
+def test_gpu_strips_backend_variants_reproduce_reference(variant):
+    """bees_q90 as two strips on cuda:0 with each knob set in the ranks
+    (read once per process, so before they import the package): every rank
+    returns the reference bytes and rank 0's counters show the path ran."""
+    env, counters = GPU_STRIP_VARIANTS[variant]
+    e = MANIFEST["e2e"]["bees_q90"]
+    res = _run_gpu_strip_ranks(e, 2, env=env, timeout=120)
+    assert len(res) == 2 and all(v[0] == e["sha256"] for v in res.values()), {r: v[0] for r, v in res.items()}
+    detail = res[0][1]
+    print(variant, {k: v for k, v in detail.items() if not k.endswith("_s")})
+    assert any(detail.get(c, 0) > 0 for c in counters), (variant, detail)
 
 
 _RCCL_CHILD = r"""
