@@ -14,6 +14,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "host/frame.h"
+#include "host/job_queue.h"
 #include "host/jpeg_encode.h"
 #include "host/jpeg_reader.h"
 #include "host/png_reader.h"
@@ -540,6 +542,30 @@ static gz_status ProcessImpl(int device, const gz_params* params, const uint8_t*
   });
 }
 
+static std::string DetailJson(const gz::ProcessResult& res) {
+  std::string j = "{";
+  char item[96];
+  for (auto& kv : res.detail) {
+    snprintf(item, sizeof(item), "%s\"%s\": %.6g", j.size() > 1 ? ", " : "", kv.first.c_str(), kv.second);
+    j += item;
+  }
+  return j + "}";
+}
+
+static void FillStats(const gz::ProcessResult& res, gz_process_stats* stats) {
+  stats->iterations = res.iterations;
+  stats->iterations_up = res.iterations_up;
+  stats->iterations_down = res.iterations_down;
+  stats->compares = res.compares;
+  stats->seconds_compare = res.seconds_compare;
+  stats->seconds_zeroing = res.seconds_zeroing;
+  stats->seconds_total = res.seconds_total;
+  stats->seconds_setup = res.seconds_setup;
+  stats->seconds_write = res.seconds_write;
+  stats->seconds_quantize = res.seconds_quantize;
+  stats->seconds_backend = res.seconds_backend;
+}
+
 // The encoded bytes (library-allocated) and statistics of a finished encode.
 static gz_status Deliver(const gz::ProcessResult& res, uint8_t** jpeg_out, size_t* jpeg_size,
                          gz_process_stats* stats) {
@@ -548,28 +574,8 @@ static gz_status Deliver(const gz::ProcessResult& res, uint8_t** jpeg_out, size_
   std::memcpy(buf, res.jpeg.data(), res.jpeg.size());
   *jpeg_out = buf;
   *jpeg_size = res.jpeg.size();
-  {
-    std::string j = "{";
-    char item[96];
-    for (auto& kv : res.detail) {
-      snprintf(item, sizeof(item), "%s\"%s\": %.6g", j.size() > 1 ? ", " : "", kv.first.c_str(), kv.second);
-      j += item;
-    }
-    g_last_detail = j + "}";
-  }
-  if (stats) {
-    stats->iterations = res.iterations;
-    stats->iterations_up = res.iterations_up;
-    stats->iterations_down = res.iterations_down;
-    stats->compares = res.compares;
-    stats->seconds_compare = res.seconds_compare;
-    stats->seconds_zeroing = res.seconds_zeroing;
-    stats->seconds_total = res.seconds_total;
-    stats->seconds_setup = res.seconds_setup;
-    stats->seconds_write = res.seconds_write;
-    stats->seconds_quantize = res.seconds_quantize;
-    stats->seconds_backend = res.seconds_backend;
-  }
+  g_last_detail = DetailJson(res);
+  if (stats) FillStats(res, stats);
   return GZ_OK;
 }
 
@@ -597,6 +603,244 @@ gz_status gz_process_jpeg(int device, const gz_params* params, const uint8_t* jp
     return Deliver(res, jpeg_out, jpeg_size, stats);
   });
 }
+
+// ---- frames ---------------------------------------------------------------
+namespace {
+// gz_frame -> the host's view of it (row_stride 0 = tight), or what is wrong.
+const char* ToFrameView(const gz_frame* frame, gz::FrameView* f) {
+  if (!frame) return "null frame";
+  f->data = static_cast<const uint8_t*>(frame->data);
+  f->w = frame->width;
+  f->h = frame->height;
+  f->channels = frame->channels;
+  f->on_device = frame->on_device != 0;
+  // (sizes and channels first: the tight stride is formed from them)
+  f->stride = 0;
+  if (f->w > 0 && f->channels > 0) f->stride = frame->row_stride ? frame->row_stride : f->row_bytes();
+  if (const char* bad = gz::FrameError(*f)) return bad;
+  return nullptr;
+}
+
+// The encode behind gz_process_frame and a gz_encoder frame job.
+gz_status EncodeFrame(int device, const gz_params* params, const gz_frame* frame, gz::ProcessResult* res) {
+  return Guard("process_frame", [&]() -> gz_status {
+    if (!params) return SetError(GZ_ERR_INVALID_ARG, "process_frame: bad argument");
+    gz::FrameView f;
+    if (const char* bad = ToFrameView(frame, &f))
+      return SetError(GZ_ERR_INVALID_ARG, std::string("process_frame: ") + bad);
+    std::string err;
+    const int rc = gz::Process(device, ToProcessParams(params), f, res, &err);
+    if (rc != 0) return SetError(rc, "process_frame: " + err);
+    return GZ_OK;
+  });
+}
+
+// The encode behind a gz_encoder file job: the reference CLI's input
+// dispatch (guetzli.cc:284-310) -- a PNG file is decoded and encoded from its
+// RGB, anything else is taken as a JPEG file.
+gz_status EncodeFile(int device, const gz_params* params, const uint8_t* data, size_t len,
+                     gz::ProcessResult* res) {
+  return Guard("process_file", [&]() -> gz_status {
+    if (!params || !data) return SetError(GZ_ERR_INVALID_ARG, "process_file: bad argument");
+    static const uint8_t kPngSig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
+    std::string err;
+    int rc;
+    if (len >= 8 && std::memcmp(data, kPngSig, 8) == 0) {
+      std::vector<uint8_t> rgb;
+      int w = 0, h = 0;
+      if (!gz::ReadPng(data, len, &w, &h, &rgb, &err))
+        return SetError(GZ_ERR_INVALID_ARG, "png_decode: " + err);
+      rc = gz::Process(device, ToProcessParams(params), rgb.data(), false, w, h, res, &err);
+    } else {
+      rc = gz::ProcessJpeg(device, ToProcessParams(params), data, len, res, &err);
+    }
+    if (rc != 0) return SetError(rc, "process_file: " + err);
+    return GZ_OK;
+  });
+}
+}  // namespace
+
+gz_status gz_process_frame(int device, const gz_params* params, const gz_frame* frame,
+                           uint8_t** jpeg_out, size_t* jpeg_size, gz_process_stats* stats) {
+  if (!jpeg_out || !jpeg_size) return SetError(GZ_ERR_INVALID_ARG, "process_frame: bad argument");
+  gz::ProcessResult res;
+  const gz_status st = EncodeFrame(device, params, frame, &res);
+  if (st != GZ_OK) return st;
+  return Deliver(res, jpeg_out, jpeg_size, stats);
+}
+
+gz_status gz_frame_pack(int device, const gz_frame* frame, uint8_t* rgb_out) {
+  return Guard("frame_pack", [&]() -> gz_status {
+    gz::FrameView f;
+    if (const char* bad = ToFrameView(frame, &f))
+      return SetError(GZ_ERR_INVALID_ARG, std::string("frame_pack: ") + bad);
+    if (!rgb_out) return SetError(GZ_ERR_INVALID_ARG, "frame_pack: bad argument");
+    std::string err;
+    const int rc = gz::PackFrameRgb(device, f, rgb_out, &err);
+    if (rc != 0) return SetError(rc, "frame_pack: " + err);
+    return GZ_OK;
+  });
+}
+
+// ---- gz_encoder -----------------------------------------------------------
+namespace {
+struct EncodeJob {
+  gz_params params;
+  bool file = false;
+  gz_frame frame;               // !file
+  const uint8_t* data = nullptr;  // file
+  size_t len = 0;
+  uint64_t tag = 0;
+};
+
+struct EncodeOutcome {
+  uint64_t tag = 0;
+  gz_status status = GZ_OK;
+  std::string error;
+  gz::ProcessResult res;
+};
+
+char* CopyString(const std::string& s) {
+  char* p = static_cast<char*>(std::malloc(s.size() + 1));
+  if (p) std::memcpy(p, s.c_str(), s.size() + 1);
+  return p;
+}
+}  // namespace
+
+struct gz_encoder {
+  using Queue = gz::JobQueue<EncodeJob, EncodeOutcome>;
+  int device = 0;
+  std::unique_ptr<Queue> queue;
+
+  // A worker's job body: the one-shot entry points' encode, inside their
+  // no-exception guard (EncodeFrame / EncodeFile), the failure text taken
+  // from this worker thread's gz_last_error.
+  EncodeOutcome Run(const EncodeJob& job) const {
+    EncodeOutcome out;
+    out.tag = job.tag;
+    out.status = job.file ? EncodeFile(device, &job.params, job.data, job.len, &out.res)
+                          : EncodeFrame(device, &job.params, &job.frame, &out.res);
+    if (out.status != GZ_OK) {
+      out.error = g_last_error;
+      out.res = gz::ProcessResult();
+    }
+    return out;
+  }
+
+  gz_status Submit(EncodeJob job, uint64_t* id_out) {
+    const uint64_t id = queue->Submit(std::move(job));
+    if (id == 0) return SetError(GZ_ERR_INVALID_ARG, "encoder_submit: the encoder is shutting down");
+    if (id_out) *id_out = id;
+    return GZ_OK;
+  }
+};
+
+// A delivered result as the C struct (library-allocated members).
+static gz_status ToResult(gz_encoder::Queue::Done& done, gz_encode_result* out) {
+  std::memset(out, 0, sizeof(*out));
+  const EncodeOutcome& o = done.result;
+  out->job = done.id;
+  out->tag = o.tag;
+  out->status = o.status;
+  out->seconds_queued = done.seconds_queued;
+  out->detail = CopyString(o.status == GZ_OK ? DetailJson(o.res) : std::string("{}"));
+  if (o.status == GZ_OK) {
+    out->jpeg = static_cast<uint8_t*>(std::malloc(o.res.jpeg.size() ? o.res.jpeg.size() : 1));
+    if (out->jpeg) std::memcpy(out->jpeg, o.res.jpeg.data(), o.res.jpeg.size());
+    out->jpeg_size = o.res.jpeg.size();
+    FillStats(o.res, &out->stats);
+  } else {
+    out->error = CopyString(o.error);
+  }
+  if (!out->detail || (o.status == GZ_OK ? !out->jpeg : !out->error)) {
+    // (the job's result is lost with the memory for it)
+    const uint64_t id = out->job;
+    gz_encode_result_free(out);
+    out->job = id;
+    out->status = GZ_ERR_OUT_OF_MEMORY;
+    return SetError(GZ_ERR_OUT_OF_MEMORY, "encoder: out of host memory");
+  }
+  return GZ_OK;
+}
+
+gz_status gz_encoder_create(const gz_encoder_options* options, gz_encoder** out) {
+  return Guard("encoder_create", [&]() -> gz_status {
+    if (!out) return SetError(GZ_ERR_INVALID_ARG, "encoder_create: bad argument");
+    *out = nullptr;
+    gz_encoder_options opt = {0, 0, 0};
+    if (options) opt = *options;
+    if (opt.device < 0 || opt.max_in_flight < 0 || opt.queue_capacity < 0)
+      return SetError(GZ_ERR_INVALID_ARG, "encoder_create: bad argument");
+    const int workers = std::min(32, std::max(1, opt.max_in_flight ? opt.max_in_flight : 8));
+    const int capacity = opt.queue_capacity ? opt.queue_capacity : 2 * workers;
+    std::unique_ptr<gz_encoder> enc(new gz_encoder);
+    enc->device = opt.device;
+    gz_encoder* self = enc.get();
+    enc->queue.reset(new gz_encoder::Queue(workers, capacity,
+                                           [self](const EncodeJob& job) { return self->Run(job); }));
+    *out = enc.release();
+    return GZ_OK;
+  });
+}
+
+gz_status gz_encoder_submit(gz_encoder* enc, const gz_params* params, const gz_frame* frame, uint64_t tag,
+                            uint64_t* job) {
+  return Guard("encoder_submit", [&]() -> gz_status {
+    if (!enc || !params || !frame) return SetError(GZ_ERR_INVALID_ARG, "encoder_submit: bad argument");
+    EncodeJob j;
+    j.params = *params;
+    j.frame = *frame;
+    j.tag = tag;
+    return enc->Submit(std::move(j), job);
+  });
+}
+
+gz_status gz_encoder_submit_file(gz_encoder* enc, const gz_params* params, const uint8_t* data, size_t len,
+                                 uint64_t tag, uint64_t* job) {
+  return Guard("encoder_submit_file", [&]() -> gz_status {
+    if (!enc || !params || !data) return SetError(GZ_ERR_INVALID_ARG, "encoder_submit_file: bad argument");
+    EncodeJob j;
+    j.params = *params;
+    j.file = true;
+    j.frame = gz_frame();
+    j.data = data;
+    j.len = len;
+    j.tag = tag;
+    return enc->Submit(std::move(j), job);
+  });
+}
+
+gz_status gz_encoder_wait(gz_encoder* enc, uint64_t job, gz_encode_result* out) {
+  return Guard("encoder_wait", [&]() -> gz_status {
+    if (!enc || !out) return SetError(GZ_ERR_INVALID_ARG, "encoder_wait: bad argument");
+    gz_encoder::Queue::Done done;
+    if (!enc->queue->Wait(job, &done))
+      return SetError(GZ_ERR_INVALID_ARG, "encoder_wait: unknown job, or its result has been delivered");
+    return ToResult(done, out);
+  });
+}
+
+gz_status gz_encoder_next(gz_encoder* enc, int block, gz_encode_result* out) {
+  return Guard("encoder_next", [&]() -> gz_status {
+    if (!enc || !out) return SetError(GZ_ERR_INVALID_ARG, "encoder_next: bad argument");
+    gz_encoder::Queue::Done done;
+    if (!enc->queue->Next(block != 0, &done)) {
+      std::memset(out, 0, sizeof(*out));
+      return GZ_OK;
+    }
+    return ToResult(done, out);
+  });
+}
+
+void gz_encode_result_free(gz_encode_result* r) {
+  if (!r) return;
+  std::free(r->error);
+  std::free(r->jpeg);
+  std::free(r->detail);
+  std::memset(r, 0, sizeof(*r));
+}
+
+void gz_encoder_destroy(gz_encoder* enc) { delete enc; }
 
 gz_status gz_jpeg_decode(const uint8_t* jpeg, size_t jpeg_len, int* width, int* height,
                          int* ncomp, int16_t** coeffs_out, size_t* ncoeffs, uint8_t** rgb_out) {

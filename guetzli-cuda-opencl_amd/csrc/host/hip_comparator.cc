@@ -42,15 +42,27 @@ namespace gz {
 
 std::unique_ptr<HipButteraugliComparator> HipButteraugliComparator::Create(
     int device, int w, int h, const uint8_t* rgb, bool device_ptr, float target, std::string* err) {
+  FrameView f;
+  f.data = rgb;
+  f.w = w;
+  f.h = h;
+  f.stride = f.row_bytes();
+  f.on_device = device_ptr;
+  return Create(device, f, target, err);
+}
+
+std::unique_ptr<HipButteraugliComparator> HipButteraugliComparator::Create(int device, const FrameView& f,
+                                                                           float target, std::string* err) {
   std::unique_ptr<HipButteraugliComparator> c(new HipButteraugliComparator);
-  c->engine_ = AcquireEngine(device, w, h, err);
+  c->engine_ = AcquireEngine(device, f.w, f.h, err);
   if (!c->engine_) return nullptr;
-  if (!c->engine_->SetReference(rgb, device_ptr)) {
+  if (!(f.tight_rgb() ? c->engine_->SetReference(f.data, f.on_device)
+                      : c->engine_->SetReferenceFrame(f.data, f.channels, f.stride))) {
     if (err) *err = c->engine_->error();
     return nullptr;
   }
-  c->w_ = w;
-  c->h_ = h;
+  c->w_ = f.w;
+  c->h_ = f.h;
   c->target_ = target;
   c->block_max_.assign(c->engine_->blocks(), 0.0f);
   return c;

@@ -6,6 +6,8 @@
 // blended on black, (v * a + 128) / 255.
 #include "host/png_reader.h"
 
+#include "host/frame.h"
+
 #include <string.h>
 #include <zlib.h>
 
@@ -127,10 +129,6 @@ inline uint32_t Sample(const uint8_t* row, size_t i, int depth) {
       return (row[bit >> 3] >> (8 - depth - (bit & 7))) & ((1u << depth) - 1);
     }
   }
-}
-
-inline uint8_t BlendOnBlack(uint8_t v, uint8_t a) {  // guetzli.cc:47-49
-  return static_cast<uint8_t>((static_cast<int>(v) * static_cast<int>(a) + 128) / 255);
 }
 
 }  // namespace

@@ -719,13 +719,85 @@ int ProcessJpegData(const ProcessParams& params, const JpegData& jpg, Comparator
   return proc.Run(jpg, err);
 }
 
+namespace {
+// The tight RGB8 image of a frame, on the host: a device frame's rows come
+// over with one (pitched) copy, RGBA is blended by PackFrame.
+bool HostPackedFrame(int device, const FrameView& frame, std::vector<uint8_t>* rgb, std::string* err) {
+  FrameView f = frame;
+  std::vector<uint8_t> rows;
+  if (f.on_device) {
+    rows.resize(f.row_bytes() * f.h);
+    if (hipSetDevice(device) != hipSuccess ||
+        (f.stride == f.row_bytes()
+             ? hipMemcpy(rows.data(), f.data, rows.size(), hipMemcpyDeviceToHost)
+             : hipMemcpy2D(rows.data(), f.row_bytes(), f.data, f.stride, f.row_bytes(), f.h,
+                           hipMemcpyDeviceToHost)) != hipSuccess) {
+      if (err) *err = "device rgb copy failed";
+      return false;
+    }
+    f.data = rows.data();
+    f.stride = f.row_bytes();
+    f.on_device = false;
+    if (f.channels == 3) {
+      rgb->swap(rows);
+      return true;
+    }
+  }
+  rgb->resize(static_cast<size_t>(3) * f.w * f.h);
+  PackFrame(f, rgb->data());
+  return true;
+}
+}  // namespace
+
 int Process(int device, const ProcessParams& params, const uint8_t* rgb, bool device_ptr, int w,
             int h, ProcessResult* result, std::string* err) {
+  FrameView f;
+  f.data = rgb;
+  f.w = w;
+  f.h = h;
+  f.stride = f.row_bytes();
+  f.on_device = device_ptr;
+  return Process(device, params, f, result, err);
+}
+
+int PackFrameRgb(int device, const FrameView& frame, uint8_t* rgb_out, std::string* err) {
+  if (const char* bad = FrameError(frame)) {
+    if (err) *err = bad;
+    return GZ_ERR_INVALID_ARG;
+  }
+  const size_t bytes = static_cast<size_t>(3) * frame.w * frame.h;
+  if (frame.on_device && frame.w >= 32 && frame.h >= 32) {
+    // what an encode's comparator holds after its import (or its copy)
+    std::string e;
+    auto cmp = HipButteraugliComparator::Create(device, frame, 1.0f, &e);
+    if (!cmp || !cmp->engine()->ReferenceRgb(rgb_out)) {
+      if (err) *err = cmp ? cmp->engine()->error() : e;
+      return GZ_ERR_DEVICE;
+    }
+    return 0;
+  }
+  if (!frame.on_device) {
+    PackFrame(frame, rgb_out);
+    return 0;
+  }
+  std::vector<uint8_t> rgb;
+  if (!HostPackedFrame(device, frame, &rgb, err)) return GZ_ERR_DEVICE;
+  std::memcpy(rgb_out, rgb.data(), bytes);
+  return 0;
+}
+
+int Process(int device, const ProcessParams& params, const FrameView& frame, ProcessResult* result,
+            std::string* err) {
   // guetzli::Process(params, stats, rgb, w, h, out), processor.cc:1157-1185
   const auto t0 = Clock::now();
   const double c0 = ThreadCpu();
+  const int w = frame.w, h = frame.h;
   if (w <= 0 || h <= 0 || w >= (1 << 16) || h >= (1 << 16)) {
     if (err) *err = "Could not create jpg data from rgb pixels";
+    return GZ_ERR_INVALID_ARG;
+  }
+  if (const char* bad = FrameError(frame)) {
+    if (err) *err = bad;
     return GZ_ERR_INVALID_ARG;
   }
   if (params.butteraugli_target > 2.0f) {
@@ -736,10 +808,23 @@ int Process(int device, const ProcessParams& params, const uint8_t* rgb, bool de
   }
   JpegData jpg;
   std::unique_ptr<HipButteraugliComparator> cmp;
-  if (w >= 32 && h >= 32) {
+  const bool search = w >= 32 && h >= 32;
+  // Packed on the host: a host frame that is not tight RGB already, and any
+  // device frame of an image too small for the search.
+  FrameView f = frame;
+  std::vector<uint8_t> host_rgb;
+  if (search ? !f.on_device && !f.tight_rgb() : f.on_device || !f.tight_rgb()) {
+    if (!HostPackedFrame(device, frame, &host_rgb, err)) return GZ_ERR_DEVICE;
+    f = FrameView();
+    f.data = host_rgb.data();
+    f.w = w;
+    f.h = h;
+    f.stride = f.row_bytes();
+  }
+  if (search) {
     // q=1 coefficients on the device from the resident reference image
     std::string e;
-    cmp = HipButteraugliComparator::Create(device, w, h, rgb, device_ptr, params.butteraugli_target, &e);
+    cmp = HipButteraugliComparator::Create(device, f, params.butteraugli_target, &e);
     if (!cmp || !cmp->OriginalJpegData(&jpg)) {
       if (err) *err = cmp ? cmp->error() : e;
       return GZ_ERR_DEVICE;
@@ -747,18 +832,7 @@ int Process(int device, const ProcessParams& params, const uint8_t* rgb, bool de
   } else {
     // Below 32 px guetzli::Process skips Butteraugli and writes the q=1
     // encode; that is the host encoder's job (no device work to mirror).
-    std::vector<uint8_t> host_rgb;
-    const uint8_t* hrgb = rgb;
-    if (device_ptr) {
-      host_rgb.resize(static_cast<size_t>(3) * w * h);
-      if (hipSetDevice(device) != hipSuccess ||
-          hipMemcpy(host_rgb.data(), rgb, host_rgb.size(), hipMemcpyDeviceToHost) != hipSuccess) {
-        if (err) *err = "device rgb copy failed";
-        return GZ_ERR_DEVICE;
-      }
-      hrgb = host_rgb.data();
-    }
-    EncodeRGBToJpegData(hrgb, w, h, &jpg);
+    EncodeRGBToJpegData(f.data, w, h, &jpg);
   }
   result->seconds_setup = Since(t0);
   const int rc = ProcessJpegData(params, jpg, cmp.get(), result, err);

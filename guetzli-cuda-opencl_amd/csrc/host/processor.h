@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "host/frame.h"
 #include "host/image420.h"
 #include "host/jpeg_model.h"
 #include "host/jpeg_writer.h"
@@ -248,6 +249,10 @@ class HipButteraugliComparator : public Comparator {
   static std::unique_ptr<HipButteraugliComparator> Create(int device, int w, int h,
                                                           const uint8_t* rgb, bool device_ptr,
                                                           float target, std::string* err);
+  // The same with the reference given as a frame: tight RGB (host or HBM),
+  // or a pitched RGB / RGBA frame in the device's HBM (Engine::SetReferenceFrame).
+  static std::unique_ptr<HipButteraugliComparator> Create(int device, const FrameView& frame, float target,
+                                                          std::string* err);
   ~HipButteraugliComparator() override { ReleaseEngine(std::move(engine_)); }
   bool Compare(const CoeffImage& img) override;
   bool StartBlockComparisons() override;
@@ -392,6 +397,16 @@ struct ProcessResult {
 // Returns 0 or a gz_status error code.
 int Process(int device, const ProcessParams& params, const uint8_t* rgb, bool device_ptr, int w,
             int h, ProcessResult* result, std::string* err);
+
+// The same for a frame (host/frame.h; FrameError(frame) must be nullptr): the
+// encode of its tight RGB8 image P.  Tight RGB takes the call above; a
+// pitched or RGBA frame in HBM with both sides >= 32 px is imported by the
+// engine (Engine::SetReferenceFrame); host frames, and device frames below
+// 32 px after a pitched copy, are packed on the host (PackFrame) first.
+int Process(int device, const ProcessParams& params, const FrameView& frame, ProcessResult* result,
+            std::string* err);
+// P of a frame (3*w*h bytes, host), by the code the encode uses.
+int PackFrameRgb(int device, const FrameView& frame, uint8_t* rgb_out, std::string* err);
 
 // guetzli::Process(params, stats, jpeg_bytes, out) (processor.cc:1029-1066):
 // ReadJpeg, CheckJpegSanity, DecodeJpegToRGB as the comparator's reference,

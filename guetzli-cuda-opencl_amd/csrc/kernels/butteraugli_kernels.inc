@@ -156,6 +156,40 @@ __global__ __launch_bounds__(256) void k_rgb_to_linear(const uint8_t* __restrict
   lin[2 * n + i] = c_tab.srgb[rgb[3 * i + 2]];
 }
 
+// A pitched RGB / RGBA frame in HBM (host/frame.h) -> its tight RGB8 image
+// and the planar linear image k_rgb_to_linear forms from that, in one pass
+// over the source.  Block (bx, y) takes 256 consecutive pixels of row y, so
+// consecutive lanes read consecutive pixels.  channels and dword are kernel
+// arguments (wave-uniform branches); dword: 4 channels with base and stride
+// 4-byte aligned, one load per pixel.  Reads the pixels' own bytes only.
+__global__ __launch_bounds__(256) void k_import_rgb8(const uint8_t* __restrict__ src, size_t stride,
+                                                     int channels, int dword, int w, int h,
+                                                     uint8_t* __restrict__ rgb, float* __restrict__ lin) {
+  const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+  if (x >= w || y >= h) return;
+  const uint8_t* p = src + static_cast<size_t>(y) * stride + static_cast<size_t>(x) * channels;
+  uint8_t r, g, b;
+  if (channels == 4) {
+    uint8_t a;
+    if (dword) {
+      const uint32_t v = *reinterpret_cast<const uint32_t*>(p);
+      r = v & 255, g = (v >> 8) & 255, b = (v >> 16) & 255, a = v >> 24;
+    } else {
+      r = p[0], g = p[1], b = p[2], a = p[3];
+    }
+    r = BlendOnBlack(r, a), g = BlendOnBlack(g, a), b = BlendOnBlack(b, a);
+  } else {
+    r = p[0], g = p[1], b = p[2];
+  }
+  const size_t n = static_cast<size_t>(w) * h, i = static_cast<size_t>(y) * w + x;
+  rgb[3 * i] = r;
+  rgb[3 * i + 1] = g;
+  rgb[3 * i + 2] = b;
+  lin[i] = c_tab.srgb[r];
+  lin[n + i] = c_tab.srgb[g];
+  lin[2 * n + i] = c_tab.srgb[b];
+}
+
 // Stages the H x W window of plane `src` at (x0, y0) into LDS `dst` (row
 // stride DS), +0 outside the image.  A thread issues all its loads before its
 // first LDS store (a load -> store -> load loop keeps one load in flight).

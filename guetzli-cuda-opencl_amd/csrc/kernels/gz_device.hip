@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../runtime/engine.h"
+#include "../host/frame.h"
 #include "../host/thread_pool.h"
 #include "gz_math.h"
 
@@ -692,6 +693,20 @@ bool Engine::SetReference(const uint8_t* rgb, bool device_ptr) {
   GZ_HIP(hipSetDevice(device_));
   GZ_HIP(hipMemcpyAsync(d_rgb_, rgb, 3 * n_, device_ptr ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
   GZ_TIMED("ref_linear", k_rgb_to_linear<<<(n_ + 255) / 256, 256, 0, s>>>(d_rgb_, n_, d_lin_));
+  return ReferenceFromLinear();
+}
+
+bool Engine::SetReferenceFrame(const uint8_t* src_dev, int channels, size_t row_stride) {
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  GZ_HIP(hipSetDevice(device_));
+  const int dword = channels == 4 && reinterpret_cast<uintptr_t>(src_dev) % 4 == 0 && row_stride % 4 == 0;
+  GZ_TIMED("ref_import", k_import_rgb8<<<dim3((w_ + 255) / 256, h_), 256, 0, s>>>(src_dev, row_stride, channels, dword,
+                                                                                   w_, h_, d_rgb_, d_lin_));
+  return ReferenceFromLinear();
+}
+
+bool Engine::ReferenceFromLinear() {
+  hipStream_t s = static_cast<hipStream_t>(stream_);
   {
     const int tx = (w_ + kOpTX - 1) / kOpTX, ty = (h_ + kOpTY - 1) / kOpTY;
     GZ_TIMED("ref_opsin", k_opsin2d<<<tx * ty, 256, 0, s>>>(d_lin_, w_, h_, tx, d_ref_xyb_, d_scales_,
@@ -700,6 +715,14 @@ bool Engine::SetReference(const uint8_t* rgb, bool device_ptr) {
   GZ_HIP(WaitIdle(s));
   ProfFlush();
   have_mask_scale_ = false;
+  return true;
+}
+
+bool Engine::ReferenceRgb(uint8_t* host_out) {
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  GZ_HIP(hipSetDevice(device_));
+  GZ_HIP(hipMemcpyAsync(host_out, d_rgb_, 3 * n_, hipMemcpyDeviceToHost, s));
+  GZ_HIP(WaitIdle(s));
   return true;
 }
 

@@ -73,6 +73,12 @@ class Engine {
 
   // Reference image (RGB8 interleaved); computes and caches its XYB.
   bool SetReference(const uint8_t* rgb, bool device_ptr);
+  // The same from a pitched RGB (channels 3) or RGBA (4, blended on black)
+  // frame in this device's HBM, rows row_stride bytes apart (host/frame.h):
+  // one import kernel instead of the copy and the linear pass.
+  bool SetReferenceFrame(const uint8_t* src_dev, int channels, size_t row_stride);
+  // The reference image as the engine holds it (tight RGB8, 3*w*h bytes).
+  bool ReferenceRgb(uint8_t* host_out);
   // q=1 coefficients of the reference ([3][blocks][64]); kept resident.
   bool SetOriginalCoeffs(const int16_t* coeffs, bool device_ptr);
   // EncodeRGBToJpeg's q=1 coefficients of the reference image (set by
@@ -305,6 +311,7 @@ class Engine {
   bool BulkApplyEnqueue(int direction, const int quant[3][64], const uint8_t* cnt_dev, const uint32_t* sel,
                         const uint8_t* last8, uint8_t* cnt_host);
   bool Fail(const char* what, int code);
+  bool ReferenceFromLinear();  // SetReference*'s tail: d_lin_ -> the cached XYB
   void ProfBegin(const char* name);
   void ProfEnd();
   void ProfMark(const char* name);

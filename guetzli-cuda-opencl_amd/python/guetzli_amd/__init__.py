@@ -55,6 +55,24 @@ class _Stats(ctypes.Structure):
                 ("seconds_backend", ctypes.c_double)]
 
 
+class _Frame(ctypes.Structure):  # gz_frame
+    _fields_ = [("data", ctypes.c_void_p), ("width", ctypes.c_int), ("height", ctypes.c_int),
+                ("channels", ctypes.c_int), ("row_stride", ctypes.c_size_t),
+                ("on_device", ctypes.c_int)]
+
+
+class _EncoderOptions(ctypes.Structure):  # gz_encoder_options
+    _fields_ = [("device", ctypes.c_int), ("max_in_flight", ctypes.c_int),
+                ("queue_capacity", ctypes.c_int)]
+
+
+class _EncodeResult(ctypes.Structure):  # gz_encode_result
+    _fields_ = [("job", ctypes.c_uint64), ("tag", ctypes.c_uint64), ("status", ctypes.c_int),
+                ("error", ctypes.c_void_p), ("jpeg", ctypes.c_void_p),
+                ("jpeg_size", ctypes.c_size_t), ("stats", _Stats),
+                ("seconds_queued", ctypes.c_double), ("detail", ctypes.c_void_p)]
+
+
 _STAGE_FIELDS = ("cand_linear", "cand_xyb", "mhic0", "mhic1", "edge", "block_dc", "block_ac",
                  "block_ac_lf", "mask", "mask_dc", "combined", "distmap")
 
@@ -81,7 +99,9 @@ EXPORTED_SYMBOLS = (
     "gz_collectives_selftest", "gz_process_jpeg", "gz_jpeg_decode", "gz_comparator_distmap",
     "gz_comparator_compare_blocks", "gz_png_decode", "gz_comparator_compare_rgb",
     "gz_comparator_compare_blocks_rgb", "gz_rccl_unique_id", "gz_rccl_create", "gz_rccl_destroy",
-    "gz_rccl_library",
+    "gz_rccl_library", "gz_process_frame", "gz_frame_pack", "gz_encoder_create", "gz_encoder_submit",
+    "gz_encoder_submit_file", "gz_encoder_wait", "gz_encoder_next", "gz_encode_result_free",
+    "gz_encoder_destroy",
 )
 
 _lib = None
@@ -193,6 +213,21 @@ def lib():
     L.gz_profile_names.restype = ctypes.c_size_t
     L.gz_last_process_detail.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
     L.gz_last_process_detail.restype = ctypes.c_size_t
+    L.gz_process_frame.argtypes = [i32, ctypes.POINTER(_Params), ctypes.POINTER(_Frame),
+                                   ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t),
+                                   ctypes.POINTER(_Stats)]
+    L.gz_frame_pack.argtypes = [i32, ctypes.POINTER(_Frame), vp]
+    L.gz_encoder_create.argtypes = [ctypes.POINTER(_EncoderOptions), ctypes.POINTER(vp)]
+    L.gz_encoder_submit.argtypes = [vp, ctypes.POINTER(_Params), ctypes.POINTER(_Frame), u64,
+                                    ctypes.POINTER(u64)]
+    L.gz_encoder_submit_file.argtypes = [vp, ctypes.POINTER(_Params), vp, ctypes.c_size_t, u64,
+                                         ctypes.POINTER(u64)]
+    L.gz_encoder_wait.argtypes = [vp, u64, ctypes.POINTER(_EncodeResult)]
+    L.gz_encoder_next.argtypes = [vp, i32, ctypes.POINTER(_EncodeResult)]
+    L.gz_encode_result_free.argtypes = [ctypes.POINTER(_EncodeResult)]
+    L.gz_encode_result_free.restype = None
+    L.gz_encoder_destroy.argtypes = [vp]
+    L.gz_encoder_destroy.restype = None
     _lib = L
     return L
 
@@ -421,6 +456,235 @@ def process_device(rgb_dev_ptr, width, height, params=None, device=0, return_sta
                                   st.seconds_total, st.seconds_setup, st.seconds_write,
                                   st.seconds_quantize, st.seconds_backend)
     return data
+
+
+def _stats(st):
+    return ProcessStats(st.iterations, st.iterations_up, st.iterations_down, st.compares,
+                        st.seconds_compare, st.seconds_zeroing, st.seconds_total, st.seconds_setup,
+                        st.seconds_write, st.seconds_quantize, st.seconds_backend)
+
+
+def _frame_layout(shape, strides, what):
+    """(h, w, channels, row stride) of an (h, w, 3|4) uint8 layout a gz_frame
+    can describe as it is -- pixel stride = channels, a positive row stride
+    -- else None."""
+    if len(shape) != 3:
+        raise GuetzliError(1, "%s: an image has the shape (h, w, 3 or 4), not %r" % (what, tuple(shape)))
+    h, w, c = (int(v) for v in shape)
+    if strides is None:
+        return h, w, c, w * c
+    rs, ps, cs = (int(v) for v in strides)
+    if cs == 1 and ps == c and rs >= w * c:
+        return h, w, c, rs
+    return None
+
+
+def _as_frame(image, device, what):
+    """gz_frame of `image` and the object that keeps its memory alive: a numpy
+    array (h, w, 3|4) uint8, or an object with __cuda_array_interface__ (a
+    torch tensor on the GPU)."""
+    cai = getattr(image, "__cuda_array_interface__", None)
+    if cai is not None:
+        if cai.get("typestr") not in ("|u1", "<u1", "u1"):
+            raise GuetzliError(1, "%s: a device image must be uint8" % what)
+        lay = _frame_layout(cai["shape"], cai.get("strides"), what)
+        if lay is None:
+            raise GuetzliError(1, "%s: device image layout (shape %r, strides %r) is not rows of "
+                               "interleaved pixels; pass image.contiguous()"
+                               % (what, tuple(cai["shape"]), cai.get("strides")))
+        if type(image).__module__.split(".")[0] == "torch":
+            import torch
+            if image.device.index is not None and image.device.index != device:
+                raise GuetzliError(1, "%s: the tensor is on device %d, the encode on device %d"
+                                   % (what, image.device.index, device))
+            # the encode reads the pixels on streams of its own
+            torch.cuda.current_stream(image.device).synchronize()
+        h, w, c, rs = lay
+        return _Frame(cai["data"][0], w, h, c, rs, 1), image
+    a = np.asarray(image, dtype=np.uint8)
+    lay = _frame_layout(a.shape, a.strides, what)
+    if lay is None:
+        a = np.ascontiguousarray(a)
+        lay = _frame_layout(a.shape, None, what)
+    h, w, c, rs = lay
+    return _Frame(a.ctypes.data, w, h, c, rs, 0), a
+
+
+def process_frame(image, params=None, device=0, return_stats=False):
+    """gz_process_frame: process() of an (h, w, 3|4) uint8 image that may have
+    padded rows and an alpha channel (blended on black, as a PNG's is) -- a
+    numpy array, or a tensor resident on the GPU (anything with
+    __cuda_array_interface__), read where it lies."""
+    L = lib()
+    fr, keep = _as_frame(image, device, "process_frame")
+    p = (params or Params())._c()
+    out, size, st = ctypes.c_void_p(), ctypes.c_size_t(), _Stats()
+    _check(L.gz_process_frame(device, ctypes.byref(p), ctypes.byref(fr), ctypes.byref(out),
+                              ctypes.byref(size), ctypes.byref(st)), "process_frame")
+    del keep
+    data = _take_bytes(out, size)
+    return (data, _stats(st)) if return_stats else data
+
+
+def frame_pack(image, device=0):
+    """gz_frame_pack: the tight RGB8 image (h, w, 3) an encode of `image` starts
+    from, produced by the code the encode uses."""
+    fr, keep = _as_frame(image, device, "frame_pack")
+    out = np.zeros((max(fr.height, 0), max(fr.width, 0), 3), dtype=np.uint8)
+    _check(lib().gz_frame_pack(device, ctypes.byref(fr), _ptr(out)), "frame_pack")
+    del keep
+    return out
+
+
+class Job:
+    """One submitted encode of an Encoder.  Holds the input's memory until
+    the result has been delivered."""
+
+    def __init__(self, encoder, job_id, tag, keep):
+        self._encoder, self.id, self.tag, self._keep = encoder, job_id, tag, keep
+        self._out = None  # (status, error, bytes, stats, seconds_queued, detail)
+
+    @property
+    def done(self):
+        return self._out is not None
+
+    def result(self, return_stats=False):
+        """The JPEG bytes (waits for them); GuetzliError(status, error) if the
+        encode failed."""
+        if self._out is None:
+            self._encoder._wait(self)
+        status, error, data, stats = self._out[:4]
+        if status != GZ_OK:
+            raise GuetzliError(status, error)
+        return (data, stats) if return_stats else data
+
+    @property
+    def seconds_queued(self):
+        self._out or self._encoder._wait(self)
+        return self._out[4]
+
+    @property
+    def detail(self):
+        import json
+        self._out or self._encoder._wait(self)
+        return json.loads(self._out[5])
+
+
+class Encoder:
+    """gz_encoder: keeps `in_flight` encodes running on one device and hands
+    the results back; the way to the library's throughput (about 8 frames in
+    flight per GPU).  submit() takes what process_frame() takes, or the bytes
+    of a PNG / JPEG file (process_file's dispatch), and blocks while
+    `queue_capacity` accepted jobs have not started."""
+
+    def __init__(self, device=0, in_flight=8, queue_capacity=0):
+        import threading
+        self.device = device
+        self._h = None
+        self._lock = threading.Lock()
+        self._jobs = {}  # id -> Job, until delivered
+        opt = _EncoderOptions(device, in_flight, queue_capacity)
+        h = ctypes.c_void_p()
+        _check(lib().gz_encoder_create(ctypes.byref(opt), ctypes.byref(h)), "encoder_create")
+        self._h = h
+        self._window = min(32, max(1, in_flight or 8))
+        self._window += queue_capacity or 2 * self._window
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def close(self):
+        """gz_encoder_destroy: jobs not started are dropped, running ones finish."""
+        if self._h:
+            h, self._h = self._h, None
+            lib().gz_encoder_destroy(h)
+            with self._lock:
+                for job in self._jobs.values():
+                    if job._out is None:
+                        job._out = (GZ_ERR_INVALID_ARG, "the encoder was closed before the result "
+                                    "was delivered", None, None, 0.0, "{}")
+                    job._keep = None
+                self._jobs.clear()
+
+    def _handle(self):
+        if not self._h:
+            raise GuetzliError(1, "the encoder is closed")
+        return self._h
+
+    def submit(self, image, params=None, tag=None):
+        L, h = lib(), self._handle()
+        p = (params or Params())._c()
+        ctag = tag if isinstance(tag, int) and 0 <= tag < 1 << 64 else 0
+        jid = ctypes.c_uint64()
+        if isinstance(image, (bytes, bytearray, memoryview)):
+            keep = bytes(image)
+            st = L.gz_encoder_submit_file(h, ctypes.byref(p), keep, len(keep), ctag, ctypes.byref(jid))
+        else:
+            fr, keep = _as_frame(image, self.device, "submit")
+            st = L.gz_encoder_submit(h, ctypes.byref(p), ctypes.byref(fr), ctag, ctypes.byref(jid))
+        _check(st, "submit")
+        job = Job(self, jid.value, tag, keep)
+        with self._lock:
+            self._jobs[job.id] = job
+        return job
+
+    def _deliver(self, r):
+        """Moves a delivered gz_encode_result into its Job."""
+        try:
+            with self._lock:
+                job = self._jobs.pop(r.job, None)
+            error = ctypes.string_at(r.error).decode() if r.error else None
+            data = ctypes.string_at(r.jpeg, r.jpeg_size) if r.jpeg else None
+            detail = ctypes.string_at(r.detail).decode() if r.detail else "{}"
+            if job is not None:
+                if isinstance(job.tag, int) and 0 <= job.tag < 1 << 64:
+                    job.tag = r.tag  # (as it came back through the queue)
+                job._out = (r.status, error, data, _stats(r.stats), r.seconds_queued, detail)
+                job._keep = None
+            return job
+        finally:
+            lib().gz_encode_result_free(ctypes.byref(r))
+
+    def _wait(self, job):
+        r = _EncodeResult()
+        st = lib().gz_encoder_wait(self._handle(), job.id, ctypes.byref(r))
+        if st != GZ_OK:
+            if job._out is not None:  # another thread's results() took it meanwhile
+                return
+            _check(st, "wait")
+        self._deliver(r)
+
+    def results(self):
+        """Finished jobs in completion order, until nothing is outstanding."""
+        while True:
+            r = _EncodeResult()
+            _check(lib().gz_encoder_next(self._handle(), 1, ctypes.byref(r)), "next")
+            if not r.job:
+                return
+            job = self._deliver(r)
+            if job is not None:
+                yield job
+
+    def map(self, images, params=None):
+        """The JPEG bytes of every image, in the images' order, with the queue
+        kept fed meanwhile (at most in_flight + queue_capacity ahead)."""
+        from collections import deque
+        pending = deque()
+        for image in images:
+            if len(pending) >= self._window:
+                yield pending.popleft().result()
+            pending.append(self.submit(image, params))
+        while pending:
+            yield pending.popleft().result()
 
 
 class Collectives:

@@ -15,12 +15,16 @@
  *    gz_last_error() (thread-local) describes it.  No call silently falls
  *    back to the CPU: without a usable HIP device they fail with
  *    GZ_ERR_DEVICE.
- *  - Images: 8-bit RGB, interleaved, row-major, no padding (3*w*h bytes).
+ *  - Images: 8-bit RGB, interleaved, row-major, no padding (3*w*h bytes);
+ *    the frame entries (gz_frame) also take padded rows and RGBA.
  *  - Coefficients: int16, [3][blocks][64], natural (row-major) order inside
  *    a block, blocks row-major with ceil(w/8) blocks per row (the layout of
  *    guetzli::JPEGComponent::coeffs, guetzli/jpeg_data.h:138-204).
- *  - One gz_comparator / gz_encoder owns one HIP stream and its device
- *    buffers; distinct objects may be used from distinct host threads.
+ *  - One gz_comparator owns one HIP stream and its device buffers; distinct
+ *    comparators may be used from distinct host threads.  A gz_encoder is a
+ *    queue of encodes on one device: its worker threads each run one encode
+ *    at a time on a pooled engine (a stream and buffers of its own), and
+ *    every one of its entry points may be called from any thread.
  */
 #ifndef GUETZLI_HIP_H_
 #define GUETZLI_HIP_H_
@@ -121,6 +125,99 @@ gz_status gz_process_rgb(int device, const gz_params* params, const uint8_t* rgb
 gz_status gz_process_rgb_device(int device, const gz_params* params, const uint8_t* rgb_dev,
                                 int width, int height, uint8_t** jpeg_out, size_t* jpeg_size,
                                 gz_process_stats* stats);
+
+/* ---- frames: padded rows, RGBA, host memory or HBM --------------------- */
+/* An input image as the caller holds it.  The image that is encoded is its
+ * tight RGB8 form P: P[y][x][c] = src[y][x][c] for 3 channels, and for 4
+ * channels the pixel blended on black as the reference's ReadPNG does
+ * (guetzli.cc:47-49): P[y][x][c] = (src[y][x][c] * src[y][x][3] + 128) / 255.
+ * Any byte alignment of data and row_stride is legal.  A device frame has
+ * been completely written before the call that names it. */
+typedef struct {
+  const void* data;     /* first byte of the top-left pixel */
+  int width, height;
+  int channels;         /* 3: RGB, 4: RGBA (8 bit, interleaved) */
+  size_t row_stride;    /* bytes from one row to the next; 0 = width*channels */
+  int on_device;        /* 0: host memory, 1: HBM of the device the call names */
+} gz_frame;
+
+/* The bytes gz_process_rgb returns for P.  A tight 3-channel frame takes the
+ * path of gz_process_rgb / gz_process_rgb_device.  Any other device frame
+ * with both sides >= 32 px is read where it lies by one import kernel (no
+ * repacking copy); host frames, and device frames under 32 px after a
+ * pitched copy, are packed on the host.  GZ_ERR_INVALID_ARG: a null pointer,
+ * channels outside {3, 4}, a row_stride that is neither 0 nor at least
+ * width*channels, sizes that are not positive or not below 65536. */
+gz_status gz_process_frame(int device, const gz_params* params, const gz_frame* frame,
+                           uint8_t** jpeg_out, size_t* jpeg_size, gz_process_stats* stats);
+/* P itself (3*w*h bytes, host memory of the caller), produced by the code an
+ * encode of `frame` uses. */
+gz_status gz_frame_pack(int device, const gz_frame* frame, uint8_t* rgb_out);
+
+/* ---- encoder: a queue that keeps N encodes in flight ------------------- */
+/* The library's throughput needs several frames in flight on a device (about
+ * 8); a gz_encoder is the worker pool and result table for that.
+ *  - Starting: jobs start in submission order on max_in_flight worker
+ *    threads; each runs the code of gz_process_frame / gz_process_jpeg.
+ *  - Lazy device use: creating an encoder does no device work and succeeds
+ *    without a GPU; a job that needs one then fails on its own with
+ *    GZ_ERR_DEVICE, and images under 32 px keep working.
+ *  - Backpressure: submit blocks while queue_capacity accepted jobs have
+ *    not started.
+ *  - Inputs: params is copied at submit; the pixel or file memory is
+ *    borrowed and must stay valid and unchanged until that job's result has
+ *    been delivered.
+ *  - Delivery: every result is delivered exactly once, by wait (that job) or
+ *    by next (finished results in completion order).  next with block == 0
+ *    and nothing finished returns GZ_OK with out->job == 0; with block == 1
+ *    it waits for a result, or returns at once with job == 0 when nothing is
+ *    outstanding, so `while (next(enc, 1, &r) == GZ_OK && r.job)` drains.
+ *    wait on an id that is unknown or already delivered returns
+ *    GZ_ERR_INVALID_ARG.  The return value of wait / next describes that
+ *    call; the encode's own outcome is out->status and out->error.  A failed
+ *    job never affects another.  Release a delivered result with
+ *    gz_encode_result_free.
+ *  - Threads: every entry point may be called from any threads at once,
+ *    except that destroy must not race with other calls on its encoder.
+ *  - Destroy: accepts nothing more, drops the jobs that have not started,
+ *    lets running encodes finish (none is cancelled), frees undelivered
+ *    results and returns when the workers have exited.
+ *  - No exception leaves a worker thread, and the CPU check of the other
+ *    entry points applies to every job.
+ *  - One device per encoder: with several GPUs create one encoder each.
+ * More than 8 same-size frames in flight make the engine pool create and
+ * destroy the extra engines per frame (it keeps 8 idle per size). */
+typedef struct gz_encoder gz_encoder;
+typedef struct {
+  int device;
+  int max_in_flight;    /* frames encoding at once = worker threads; 0 = 8; clamped to [1, 32] */
+  int queue_capacity;   /* accepted jobs not yet started; 0 = 2 * max_in_flight */
+} gz_encoder_options;
+
+typedef struct {
+  uint64_t job;         /* id from submit; ids start at 1; 0 = "no result" */
+  uint64_t tag;         /* the caller's */
+  gz_status status;     /* of the encode */
+  char* error;          /* NULL when status == GZ_OK */
+  uint8_t* jpeg;
+  size_t jpeg_size;
+  gz_process_stats stats;
+  double seconds_queued;   /* submit -> a worker took it */
+  char* detail;            /* the JSON gz_last_process_detail would give */
+} gz_encode_result;
+
+gz_status gz_encoder_create(const gz_encoder_options* options, gz_encoder** out);
+gz_status gz_encoder_submit(gz_encoder* enc, const gz_params* params, const gz_frame* frame,
+                            uint64_t tag, uint64_t* job);
+/* PNG or JPEG file bytes: a PNG is decoded (gz_png_decode) and encoded from
+ * its RGB, anything else is taken as a JPEG file (gz_process_jpeg). */
+gz_status gz_encoder_submit_file(gz_encoder* enc, const gz_params* params, const uint8_t* data,
+                                 size_t len, uint64_t tag, uint64_t* job);
+gz_status gz_encoder_wait(gz_encoder* enc, uint64_t job, gz_encode_result* out);
+gz_status gz_encoder_next(gz_encoder* enc, int block, gz_encode_result* out);
+/* Frees error, jpeg and detail and zeroes the struct. */
+void gz_encode_result_free(gz_encode_result* result);
+void gz_encoder_destroy(gz_encoder* enc);
 
 /* Encodes a JPEG file: guetzli::Process(params, stats, jpeg_bytes, out)
  * (guetzli/processor.h:44-46, processor.cc:1029-1066) -- the input's own
