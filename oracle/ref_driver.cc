@@ -8,8 +8,8 @@
 //
 //   guetzli_ref encode  RGB W H QUALITY OUT.jpg [c|cpu] [lookahead=N new_model=0|1
 //                       try_420=0|1 force_420=0|1]       guetzli.cc:247-368
-//   guetzli_ref stages  RGB W H QSEED OUTDIR [nozero]        see Stages()
-//   guetzli_ref zero_variants RGB W H QSEED OUTDIR           see ZeroVariants()
+//   guetzli_ref stages  RGB W H QSEED OUTDIR [nozero] [qmul=N] see Stages()
+//   guetzli_ref zero_variants RGB W H QSEED OUTDIR [qmul=N]  see ZeroVariants()
 //   guetzli_ref encode_jpeg IN.jpg QUALITY OUT.jpg            processor.cc:1029-1066
 //   guetzli_ref decode  IN.jpg OUT.rgb OUT.coeffs             ReadJpeg + DecodeJpegToRGB
 //
@@ -166,15 +166,30 @@ int Decode(int argc, char** argv) {
 }
 
 // Deterministic quantization matrix for stage fixtures (any valid matrix
-// exercises the same code; it only needs to be reproducible).
-void MakeQ(int seed, int q[3][64]) {
+// exercises the same code; it only needs to be reproducible).  qmul scales
+// every entry: 1 is the fine matrix of the ordinary fixtures, a large value
+// a coarse one whose candidate lies far from the original.
+void MakeQ(int seed, int q[3][64], int qmul = 1) {
   uint32_t s = 2463534242u ^ static_cast<uint32_t>(seed * 7919);
   for (int c = 0; c < 3; ++c)
     for (int k = 0; k < 64; ++k) {
       s ^= s << 13; s ^= s >> 17; s ^= s << 5;
       int zz = guetzli::kJPEGZigZagOrder[k];
-      q[c][k] = 1 + (zz * (2 + c)) / 8 + static_cast<int>(s % 3);
+      q[c][k] = (1 + (zz * (2 + c)) / 8 + static_cast<int>(s % 3)) * qmul;
     }
+}
+
+// Optional trailing arguments of `stages` / `zero_variants` (argv[7] on, any
+// order): "nozero" and "qmul=N".  Returns false on anything else.
+bool StageOptions(int argc, char** argv, bool* nozero, int* qmul) {
+  *nozero = false;
+  *qmul = 1;
+  for (int i = 7; i < argc; ++i) {
+    if (!strcmp(argv[i], "nozero")) *nozero = true;
+    else if (!strncmp(argv[i], "qmul=", 5) && atoi(argv[i] + 5) >= 1) *qmul = atoi(argv[i] + 5);
+    else return false;
+  }
+  return true;
 }
 
 // Per-block greedy zeroing orders of every block (the CPU_OPT loop of
@@ -223,11 +238,11 @@ std::vector<guetzli::CoeffData> ZeroOrders(const std::vector<uint8_t>& rgb, int 
 // Candidate image of the stage fixtures: EncodeRGBToJpeg -> remove quant ->
 // copy -> global quantization (processor.cc:1160-1163, 94-107, 310-317).
 bool StageCandidate(const std::vector<uint8_t>& rgb, int w, int h, int qseed,
-                    guetzli::JPEGData* jpg, guetzli::OutputImage* img, int q[3][64]) {
+                    guetzli::JPEGData* jpg, guetzli::OutputImage* img, int q[3][64], int qmul) {
   if (!guetzli::EncodeRGBToJpeg(rgb, w, h, jpg)) return false;
   int q_in[3][64];
   guetzli::RemoveOriginalQuantization(jpg, q_in);
-  MakeQ(qseed, q);
+  MakeQ(qseed, q, qmul);
   img->CopyFromJpegData(*jpg);
   img->ApplyGlobalQuantization(q);
   return true;
@@ -241,12 +256,15 @@ int ZeroVariants(int argc, char** argv) {
   std::vector<uint8_t> rgb = ReadAll(argv[2]);
   const int w = atoi(argv[3]), h = atoi(argv[4]), qseed = atoi(argv[5]);
   const std::string dir = argv[6];
+  bool nozero;
+  int qmul;
+  if (!StageOptions(argc, argv, &nozero, &qmul)) return 1;
   g_mathMode = MODE_CPU_OPT;
   const float target = static_cast<float>(guetzli::ButteraugliScoreForQuality(95));
   guetzli::JPEGData jpg;
   guetzli::OutputImage img(w, h);
   int q[3][64];
-  if (!StageCandidate(rgb, w, h, qseed, &jpg, &img, q)) return 4;
+  if (!StageCandidate(rgb, w, h, qseed, &jpg, &img, q, qmul)) return 4;
   static const int kVariants[][3] = {{1, 7, 1}, {2, 7, 1}, {3, 1, 1}, {3, 6, 1}, {3, 7, 0}, {2, 6, 0}};
   for (const auto& v : kVariants) {
     std::vector<guetzli::CoeffData> out = ZeroOrders(rgb, w, h, target, jpg, &img, v[0], v[1], v[2] != 0);
@@ -262,6 +280,9 @@ int Stages(int argc, char** argv) {
   std::vector<uint8_t> rgb = ReadAll(argv[2]);
   const int w = atoi(argv[3]), h = atoi(argv[4]), qseed = atoi(argv[5]);
   const std::string dir = argv[6];
+  bool nozero;
+  int qmul;
+  if (!StageOptions(argc, argv, &nozero, &qmul)) return 1;
   g_mathMode = MODE_CPU_OPT;
   const float target = static_cast<float>(guetzli::ButteraugliScoreForQuality(95));
 
@@ -272,13 +293,14 @@ int Stages(int argc, char** argv) {
   int q_in[3][64];
   guetzli::RemoveOriginalQuantization(&jpg, q_in);
   int q[3][64];
-  MakeQ(qseed, q);
+  MakeQ(qseed, q, qmul);
   guetzli::OutputImage img(w, h);
   img.CopyFromJpegData(jpg);
   img.ApplyGlobalQuantization(q);
 
   FILE* meta = fopen((dir + "/meta.txt").c_str(), "w");
   fprintf(meta, "w %d\nh %d\nqseed %d\ntarget %.9g\n", w, h, qseed, target);
+  if (qmul != 1) fprintf(meta, "qmul %d\n", qmul);  // absent = 1: the fine fixtures' meta.txt is unchanged
   WriteAll(dir + "/q.i32", &q[0][0], sizeof(q));
   {
     std::vector<int16_t> orig;
@@ -365,9 +387,9 @@ int Stages(int argc, char** argv) {
   }
 
   // Per-block greedy zeroing order, CPU_OPT loop of SelectFrequencyMasking
-  // (processor.cc:641-672) with comp_mask 7, factor 1 (argv[7] "nozero":
-  // skipped -- the frame-size stage hashes, tests/golden/make_stage_hashes.py).
-  if (!(argc > 7 && !strcmp(argv[7], "nozero"))) {
+  // (processor.cc:641-672) with comp_mask 7, factor 1 ("nozero": skipped --
+  // the frame-size stage hashes, tests/golden/make_stage_hashes.py).
+  if (!nozero) {
     std::vector<guetzli::CoeffData> out = ZeroOrders(rgb, w, h, target, jpg, &img, 3, 7, true);
     WriteAll(dir + "/zero_order.bin", out.data(), out.size() * sizeof(out[0]));
   }
@@ -385,6 +407,7 @@ int main(int argc, char** argv) {
   if (argc >= 2 && !strcmp(argv[1], "decode")) return Decode(argc, argv);
   fprintf(stderr,
           "usage: guetzli_ref encode RGB W H QUALITY OUT.jpg [c|cpu]\n"
-          "       guetzli_ref stages RGB W H QSEED OUTDIR\n");
+          "       guetzli_ref stages RGB W H QSEED OUTDIR [nozero] [qmul=N]\n"
+          "       guetzli_ref zero_variants RGB W H QSEED OUTDIR [qmul=N]\n");
   return 1;
 }

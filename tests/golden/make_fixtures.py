@@ -12,14 +12,27 @@ except those files.
                    combined maps, distmap, block weights, per-block zeroing
                    orders (+ zero_order_la*_m*_nm*.bin: lookahead / comp_mask /
                    zeroing-model variants).
+                   The x_ cases are extreme inputs (black, white, checkerboards,
+                   saturated primaries, full-range noise, ramps to 0 / 255); the
+                   _coarse ones quantize 24 times coarser (far-off candidates).
+                   They are hashed fixtures: input, coefficients, block weights
+                   and meta.txt as files, every plane and zeroing order as the
+                   sha256 of the reference's bytes (sha256.txt); the reader
+                   re-forms those with the CPU oracle and checks the hash.
   manifest.json    end-to-end known answers: sha256 / size / iterations of
                    `guetzli --c` on bees.png and on synthetic frames.
+
+  python tests/golden/make_fixtures.py [stages] [zero-variants] [e2e-small]
+      [e2e-params] [e2e-params-la] [e2e-420] [e2e-420-la] [e2e-edge]
+      [e2e-extreme] [e2e-420-1080] [e2e-420-synth]
 """
 import hashlib
 import json
 import os
+import shutil
 import subprocess
 import sys
+import tempfile
 
 import numpy as np
 
@@ -63,29 +76,134 @@ def bees_crop(x0, y0, w, h):
     return np.ascontiguousarray(bees[y0:y0 + h, x0:x0 + w])
 
 
+# Extreme inputs (the x_ cases): every one holds samples 0 and 255, which the
+# texture / bees / flat cases (31..239) and gz.synthetic_frame (16..240) never
+# do.  black / white: a constant frame at either end of the sRGB table,
+# distance exactly 0, |DC| 1024 / 1017.  checker: 0/255 per pixel and per 8x8
+# block (the largest AC a frame can hold).  primaries: saturated colours on
+# 7-pixel bars, off the block grid.  fullrange: uniform noise over all 256
+# values, odd size, blocks with up to 178 of 192 coefficients non-zero.
+# ramp: slow gradients that start at 0 or end at 255 in every channel.
+def black():
+    return np.zeros((32, 40, 3), np.uint8)
+
+
+def white():
+    return np.full((32, 40, 3), 255, np.uint8)
+
+
+def checker():
+    """rows 0..19: per-pixel 0/255 checkerboard; rows 20..39: 8x8-block checkerboard"""
+    yy, xx = np.mgrid[0:40, 0:48]
+    a = (((xx + yy) & 1) * 255).astype(np.uint8)
+    b = ((((xx // 8) + (yy // 8)) & 1) * 255).astype(np.uint8)
+    img = np.stack([a, a, a], -1)
+    img[20:] = np.stack([b, b, b], -1)[20:]
+    return img
+
+
+def primaries():
+    """7-px bars of saturated primaries (off the 8 grid), mirrored + channel-swapped
+    lower half, every 5th row inverted"""
+    cols = np.array([[255, 0, 0], [0, 255, 0], [0, 0, 255], [255, 255, 0], [0, 255, 255],
+                     [255, 0, 255], [0, 0, 0], [255, 255, 255]], np.uint8)
+    img = np.zeros((48, 64, 3), np.uint8)
+    for x in range(64):
+        img[:, x] = cols[(x // 7) % 8]
+    img[24:] = img[24:, ::-1][:, :, ::-1]
+    img[::5, :, :] = 255 - img[::5]
+    return img
+
+
+def fullrange():
+    """uniform noise over all 256 values, odd size"""
+    return np.random.default_rng(77).integers(0, 256, (41, 56, 3), dtype=np.uint8)
+
+
+def ramp():
+    """slow gradients that start at 0 or end at 255 in every channel"""
+    yy, xx = np.mgrid[0:33, 0:64]
+    img = np.zeros((33, 64, 3), np.uint8)
+    img[..., 0] = np.clip(xx * 4 + yy // 8, 0, 255)
+    img[..., 1] = np.clip(255 - xx * 4 - yy // 8, 0, 255)
+    img[..., 2] = np.clip(yy * 8, 0, 255)
+    return img
+
+
 STAGE_CASES = [
-    # name, image factory, qseed
+    # name, image factory, qseed[, qmul]: qmul scales the candidate's
+    # quantization matrix (oracle/ref_driver.cc MakeQ; 1 when absent)
     ("tex_64x48", lambda: texture_image(64, 48, 1), 1),
     ("tex_100x77", lambda: texture_image(100, 77, 2), 2),
     ("tex_41x33", lambda: texture_image(41, 33, 3), 3),
     ("bees_88x64", lambda: bees_crop(200, 100, 88, 64), 4),
     ("flat_48x40", lambda: flat_image(48, 40, 5), 5),
+    ("x_black_40x32", black, 11),
+    ("x_white_40x32", white, 12),
+    ("x_checker_48x40", checker, 13),
+    ("x_primaries_64x48", primaries, 14),
+    ("x_fullrange_56x41", fullrange, 15),
+    ("x_ramp_64x33", ramp, 16),
+    # far-off candidates: the same images under a 24 times coarser matrix
+    # (distance 13.7 and 11.6, against at most 1.4 for every case above)
+    ("x_primaries_64x48_coarse", primaries, 14, 24),
+    ("x_fullrange_56x41_coarse", fullrange, 15, 24),
 ]
+EXTREME_BASE = ["x_black_40x32", "x_white_40x32", "x_checker_48x40", "x_primaries_64x48",
+                "x_fullrange_56x41", "x_ramp_64x33"]
+
+
+def qmul_args(case):
+    return ["qmul=%d" % case[3]] if len(case) > 3 and case[3] != 1 else []
 
 
 def sha256(path):
     return hashlib.sha256(open(path, "rb").read()).hexdigest()
 
 
+# The x_ cases are committed as hashed fixtures (tests/oracle_lib.py Fixture):
+# of the reference's dump only these files, and the sha256 of every other one
+# (the float planes and the zeroing orders, 95 % of a dump) in sha256.txt.
+HASHED_KEEP = ("input.rgb", "meta.txt", "orig_coeffs.i16", "cand_coeffs.i16")
+
+
+def is_hashed(name):
+    return name.startswith("x_")
+
+
+def keep_file(f):
+    return f in HASHED_KEEP or f.startswith("weights_")
+
+
+def record_hashes(d, dump):
+    """Copies the kept files of the reference's dump directory into the
+    fixture directory d and merges the other files' sha256 into d/sha256.txt."""
+    path = os.path.join(d, "sha256.txt")
+    hashes = dict(l.split() for l in open(path)) if os.path.exists(path) else {}
+    for f in sorted(os.listdir(dump)):
+        if keep_file(f):
+            shutil.copyfile(os.path.join(dump, f), os.path.join(d, f))
+        else:
+            hashes[f] = sha256(os.path.join(dump, f))
+    with open(path, "w") as out:
+        for f in sorted(hashes):
+            out.write("%s %s\n" % (f, hashes[f]))
+
+
 def run_stages():
-    for name, make, qseed in STAGE_CASES:
+    for case in STAGE_CASES:
+        name, make, qseed = case[:3]
         img = make()
         h, w, _ = img.shape
         d = os.path.join(HERE, "stages_" + name)
         os.makedirs(d, exist_ok=True)
         rgb = os.path.join(d, "input.rgb")
         img.tofile(rgb)
-        subprocess.run([REF, "stages", rgb, str(w), str(h), str(qseed), d], check=True)
+        dump = tempfile.mkdtemp(prefix="gz_stages_") if is_hashed(name) else d
+        subprocess.run([REF, "stages", rgb, str(w), str(h), str(qseed), dump] + qmul_args(case), check=True)
+        if dump != d:
+            record_hashes(d, dump)
+            shutil.rmtree(dump)
         print("stages", name, w, h)
 
 
@@ -93,11 +211,16 @@ def run_zero_variants():
     """zero_order_la<L>_m<M>_nm<N>.bin next to each stage fixture: the
     per-block zeroing orders for lookahead 1/2, comp_mask 1/6 and the old
     zeroing model (oracle/ref_driver.cc ZeroVariants)."""
-    for name, _, qseed in STAGE_CASES:
+    for case in STAGE_CASES:
+        name, _, qseed = case[:3]
         d = os.path.join(HERE, "stages_" + name)
         meta = dict(l.split() for l in open(os.path.join(d, "meta.txt")) if len(l.split()) == 2)
+        dump = tempfile.mkdtemp(prefix="gz_stages_") if is_hashed(name) else d
         subprocess.run([REF, "zero_variants", os.path.join(d, "input.rgb"), meta["w"], meta["h"],
-                        str(qseed), d], check=True)
+                        str(qseed), dump] + qmul_args(case), check=True)
+        if dump != d:
+            record_hashes(d, dump)
+            shutil.rmtree(dump)
         print("zero variants", name)
 
 
@@ -140,7 +263,7 @@ def main():
         run_zero_variants()
     if "e2e-small" in what:
         cases = [("bees_q95", os.path.join(HERE, "bees.rgb"), 444, 258, 95)]
-        for name, _, _ in STAGE_CASES:
+        for name in [c[0] for c in STAGE_CASES if not c[0].startswith("x_")]:
             d = os.path.join(HERE, "stages_" + name)
             meta = dict(l.split() for l in open(os.path.join(d, "meta.txt")) if len(l.split()) == 2)
             cases.append(("%s_q95" % name, os.path.join(d, "input.rgb"), int(meta["w"]),
@@ -241,6 +364,22 @@ def main():
                   ("gray_96x64_q95_try420", g1[0], g1[1], g1[2], 95, {"try_420": 1}),
                   ("gray_bees_88x64_q95", g2[0], g2[1], g2[2], 95)]
         run_e2e(manifest, cases, section="e2e_edge")
+    if "e2e-extreme" in what:
+        # the extreme stage images end to end: 4:4:4 at q95 and q84, and the
+        # 4:2:0 pass at q90.  black / white / checker are gray, so force_420
+        # takes the one-component continuation (e2e_edge, which the CPU host
+        # loop runs too); the three coloured ones are real 4:2:0 encodes.
+        def stage(name):
+            d = os.path.join(HERE, "stages_" + name)
+            meta = dict(l.split() for l in open(os.path.join(d, "meta.txt")) if len(l.split()) == 2)
+            return os.path.join(d, "input.rgb"), int(meta["w"]), int(meta["h"])
+
+        run_e2e(manifest, [("%s_q%d" % (name, q),) + stage(name) + (q,)
+                           for name in EXTREME_BASE for q in (95, 84)])
+        run_e2e(manifest, [("%s_q90_force420" % name,) + stage(name) + (90, {"force_420": 1})
+                           for name in EXTREME_BASE[:3]], section="e2e_edge")
+        run_e2e(manifest, [("%s_q90_force420" % name,) + stage(name) + (90, {"force_420": 1})
+                           for name in EXTREME_BASE[3:]], section="e2e_420")
     if "e2e-420-1080" in what:
         # the 4:2:0 pass at full size: synthetic 1920x1080 seed 0 (the bench's
         # frame), q95, force_420 -- about 7 minutes of reference CPU time

@@ -3,9 +3,14 @@
 Test infrastructure: only tests/, __graft_entry__.smoke() and bench.py's
 cpu_baseline leg import this module.
 """
+import atexit
 import ctypes
+import hashlib
 import os
+import re
+import shutil
 import subprocess
+import tempfile
 
 import numpy as np
 
@@ -78,11 +83,35 @@ def fixture_cases():
     return sorted(d[len("stages_"):] for d in os.listdir(GOLDEN) if d.startswith("stages_"))
 
 
+_derived_dir = None  # this process's copies of the hashed fixtures' planes
+
+
+def _derived_path(case, name):
+    global _derived_dir
+    if _derived_dir is None:
+        _derived_dir = tempfile.mkdtemp(prefix="gz_fixture_")
+        atexit.register(shutil.rmtree, _derived_dir, True)
+    os.makedirs(os.path.join(_derived_dir, case), exist_ok=True)
+    return os.path.join(_derived_dir, case, name)
+
+
 class Fixture:
-    """Reader for one tests/golden/stages_<case>/ directory."""
+    """Reader for one tests/golden/stages_<case>/ directory.
+
+    A directory with a sha256.txt is a hashed fixture: of the reference's
+    dump it keeps the input, the coefficients, the block weights and meta.txt
+    as files and every float plane and zeroing order only as the sha256 of the
+    reference's bytes (they are 95 % of a dump's size).  path() of such a
+    name forms the plane with the CPU oracle, fails unless its bytes hash to
+    the reference's, and hands out a file with exactly those bytes -- so a
+    reader sees the reference's dump, byte for byte, or an error."""
 
     def __init__(self, case):
+        self.case = case
         self.dir = os.path.join(GOLDEN, "stages_" + case)
+        self.hashes = {}
+        if os.path.exists(os.path.join(self.dir, "sha256.txt")):
+            self.hashes = dict(line.split() for line in open(os.path.join(self.dir, "sha256.txt")))
         meta = {}
         for line in open(os.path.join(self.dir, "meta.txt")):
             k, v = line.split()
@@ -95,7 +124,44 @@ class Fixture:
         self.rw, self.rh = (self.w + 2) // 3, (self.h + 2) // 3
 
     def path(self, name):
-        return os.path.join(self.dir, name)
+        if name not in self.hashes:
+            return os.path.join(self.dir, name)
+        out = _derived_path(self.case, name)
+        if not os.path.exists(out):
+            self._derive(name)
+        return out
+
+    def _store(self, name, arr):
+        data = np.ascontiguousarray(arr).tobytes()
+        assert hashlib.sha256(data).hexdigest() == self.hashes[name], (
+            "stages_%s/%s: the oracle's bytes differ from the reference's (sha256)" % (self.case, name))
+        with open(_derived_path(self.case, name), "wb") as f:
+            f.write(data)
+
+    def _derive(self, name):
+        L = lib()
+        w, h, n = self.w, self.h, self.w * self.h
+        rgb = self.rgb()
+        zo = re.match(r"zero_order(?:_la(\d+)_m(\d+)_nm(\d+))?\.bin$", name)
+        if zo:
+            la, mask, new_model = [int(v) for v in zo.groups()] if zo.group(1) else (3, 7, 1)
+            out = np.zeros(self.nb * 192, COEFF_DTYPE)
+            L.gzo_block_zeroing_orders(w, h, rgb, self.f32("ref_mask.f32"), self.i16("cand_coeffs.i16"),
+                                       self.i16("orig_coeffs.i16"), ctypes.c_float(self.target), la, mask,
+                                       new_model, out.ctypes.data)
+            self._store(name, out)
+            return
+        # every plane of one Compare, and the reference's mask against itself
+        st = oracle_compare_planes(w, h, rgb, self.i16("cand_coeffs.i16"))
+        assert np.float32(st.pop("distance")) == np.float32(self.meta["distance"]), self.case
+        m = np.zeros(3 * n, np.float32)
+        L.gzo_mask(w, h, st["ref_xyb"].copy(), st["ref_xyb"].copy(), m, np.zeros(3 * n, np.float32))
+        st["ref_mask"] = m
+        for k, arr in st.items():
+            f = "cand_srgb.u8" if k == "cand_srgb" else k + ".f32"
+            if f in self.hashes:
+                self._store(f, arr)
+        assert os.path.exists(_derived_path(self.case, name)), name
 
     def f32(self, name):
         return np.fromfile(self.path(name), dtype=np.float32)
@@ -114,6 +180,66 @@ class Fixture:
         zero_order_la<L>_m<M>_nm<N>.bin (make_fixtures.py zero-variants)."""
         name = "zero_order.bin" if variant is None else "zero_order_la%d_m%d_nm%d.bin" % variant
         return np.fromfile(self.path(name), dtype=COEFF_DTYPE).reshape(self.nb, 192)
+
+
+def oracle_compare_planes(w, h, rgb, coeffs):
+    """One Compare on the CPU oracle, stage by stage (the chain
+    test_oracle_compare_stages_bit_exact pins against the reference):
+    gzo_coeffs_to_srgb -> gzo_srgb_to_linear_planes -> gzo_opsin_dynamics ->
+    gzo_diffmap with a Stages struct.  Returns every plane the device's
+    compare_stages() returns, under the same names, the reference image's
+    "ref_xyb", the candidate's "cand_srgb" bytes and "distance"."""
+    L = lib()
+    n = w * h
+    rn = ((w + 2) // 3) * ((h + 2) // 3)
+    rgb = np.ascontiguousarray(rgb, np.uint8).ravel()
+    coeffs = np.ascontiguousarray(coeffs, np.int16).ravel()
+    ref = np.zeros(3 * n, np.float32)
+    L.gzo_srgb_to_linear_planes(w, h, rgb, ref)
+    L.gzo_opsin_dynamics(w, h, ref)
+    srgb = np.zeros(3 * n, np.uint8)
+    L.gzo_coeffs_to_srgb(w, h, coeffs, srgb)
+    cand = np.zeros(3 * n, np.float32)
+    L.gzo_srgb_to_linear_planes(w, h, srgb, cand)
+    out = {"ref_xyb": ref.copy(), "cand_srgb": srgb, "cand_linear": cand.copy()}
+    L.gzo_opsin_dynamics(w, h, cand)
+    out["cand_xyb"] = cand.copy()
+    sizes = dict(mhic0=3 * n, mhic1=3 * n, edge=3 * rn, block_dc=3 * rn, block_ac=3 * rn,
+                 block_ac_lf=3 * rn, mask=3 * n, mask_dc=3 * n, combined=rn)
+    arrs = {k: np.zeros(v, np.float32) for k, v in sizes.items()}
+    st = Stages(**{k: a.ctypes.data for k, a in arrs.items()})
+    dm = np.zeros(n, np.float32)
+    if L.gzo_diffmap(w, h, ref, cand, dm, ctypes.addressof(st)) != 1:
+        raise RuntimeError("gzo_diffmap failed")
+    out.update(arrs)
+    out["distmap"] = dm
+    out["distance"] = L.gzo_compare(w, h, rgb, coeffs, np.zeros(n, np.float32))
+    return out
+
+
+SQRT_DOMAIN = 2.0 ** 96  # sqrt_cr_big is correctly rounded on [0, 2^96) (tests/native/sqrt_check.hip)
+
+
+def block_diff_sqrt_operand_bound(m):
+    """Upper bound of every operand k_block_diff2 hands to sqrt_cr_big, given
+    m >= |v| for every value v of the MHIC planes (mhic0, mhic1).
+
+    The Y operands (butteraugli_kernels.inc, bd2_half / bd_columns_part):
+      - fill() stages t = a + b or a - b of two MHIC values: |t| <= 2 m (2 m is
+        a float when m is, so rounding cannot pass it);
+      - the row and column 8-point FFTs (real_fft8, fft8_inplace) are
+        unnormalised, run on the unhalved tile: each of re, im of a bin of the
+        8x8 window is sum_{y,x} c t with |c| <= 1, so |re|, |im| <= 64 * 2 m =
+        128 m in exact arithmetic.  Every intermediate is such a sum over a
+        subset, so each of the fewer than 100 roundings on the way adds at
+        most 2^-24 * 128 m: the computed values stay below 128 m (1 + 2^-17);
+      - v = (re * re + im * im) * kBdVScaleY with kBdVScaleY = 0.000064f *
+        0.25f * 2^32: v <= 2 (128 m)^2 * 0.000016 * 2^32 * (1 + 2^-16), the
+        last factor covering the squares of the above and v's three roundings.
+    So the operand is below 2^96 while m < 5.9e9; the planes hold a few
+    hundred at most."""
+    m = float(m)
+    return 2.0 * (128.0 * m) ** 2 * (float(np.float32(0.000064)) * 0.25 * 2.0 ** 32) * (1.0 + 2.0 ** -16)
 
 
 # (lookahead, comp_mask, new_zeroing_model) of the committed zeroing variants

@@ -4,7 +4,11 @@ Bit-exact against fixtures produced by the reference itself (oracle/_ref):
 every stage of one Butteraugli pass, the block-corner activity mask, the
 per-block greedy zeroing orders, and end-to-end JPEG bytes (sha256) of
 `guetzli --c` on bees.png and synthetic frames.  Larger frames are checked
-against the CPU oracle at sizes it finishes in seconds.
+against the CPU oracle at sizes it finishes in seconds.  The stage fixtures
+named x_* are extreme inputs (black, white, 0/255 checkerboards, saturated
+primaries, full-range noise, ramps into 0 and 255) and their *_coarse twins
+candidates a 24 times coarser quantization away; candidates farther still
+and fully dense blocks are checked against the oracle.
 """
 import hashlib
 import json
@@ -13,7 +17,8 @@ import os
 import numpy as np
 import pytest
 
-from oracle_lib import COEFF_DTYPE, GOLDEN, ZERO_VARIANTS, Fixture, fixture_cases, lib as oracle
+from oracle_lib import (COEFF_DTYPE, GOLDEN, SQRT_DOMAIN, ZERO_VARIANTS, Fixture,
+                        block_diff_sqrt_operand_bound, fixture_cases, lib as oracle, oracle_compare_planes)
 
 pytestmark = pytest.mark.gpu
 
@@ -718,3 +723,127 @@ def test_block_diff_sqrt_and_interp_exhaustive(which):
     rc = lib.gz_helper_check(0 if which == "sqrt" else 1, tab.ctypes.data_as(ctypes.c_void_p), out)
     assert rc == 0
     assert out[0] == 0, "%d mismatches, first bit pattern %#010x" % (out[0], out[1])
+
+
+FAR_REFERENCES = ["x_checker_48x40", "x_primaries_64x48", "x_black_40x32", "x_white_40x32",
+                  "x_fullrange_56x41"]
+
+
+def _far_candidates(F):
+    """Four candidates no quantization produces, [3][blocks][64] int16 each:
+    flat gray; uniform noise over [-1023, 1023] at every position (the IDCT
+    overshoots both clamps of k_coeffs_to_srgb8 on about half the samples);
+    the original with its DC negated and no AC; no AC and a DC drawn from
+    {-2047, 2047, -1024, 1016} (past the coefficient range, at it, and the
+    white frame's DC less one step)."""
+    rng = np.random.default_rng(2024)
+    orig = F.i16("orig_coeffs.i16").reshape(3, F.nb, 64)
+    zero = np.zeros_like(orig)
+    noise = rng.integers(-1023, 1024, size=orig.shape).astype(np.int16)
+    negdc = np.zeros_like(orig)
+    negdc[:, :, 0] = -orig[:, :, 0]
+    drawn = np.zeros_like(orig)
+    drawn[:, :, 0] = rng.choice(np.array([-2047, 2047, -1024, 1016], np.int16), size=(3, F.nb))
+    return [("zero", zero), ("noise", noise), ("negated_dc", negdc), ("drawn_dc", drawn)]
+
+
+@pytest.mark.parametrize("case", FAR_REFERENCES)
+def test_compare_far_candidates_match_oracle(gz, case):
+    """Candidates at distance 18 to 329 from a black, white, checkerboard,
+    saturated or full-range reference (the stage fixtures stop at 13.7): every
+    compare_stages plane, every plane of the search's own kernels, the
+    distance of the graph-launched pass (twice: capture and replay) and the
+    per-block maxima equal the CPU oracle's bit for bit.  The oracle is the
+    reference here -- it is pinned on the same images, fine and coarse, by
+    test_oracle_compare_stages_bit_exact.  These inputs put the clamps of
+    k_coeffs_to_srgb8, both ends of the sRGB table, interp_pair_f past its
+    table and sqrt_cr_big at exact zeros (black against flat gray: the whole
+    X plane) and at the pipeline's largest operands on the device path.
+
+    The square roots' domain, asserted: every operand k_block_diff2 hands to
+    sqrt_cr_big is at most 2 (128 M)^2 * 0.000016 * 2^32 * (1 + 2^-16), M the
+    largest |value| of the dumped mhic0 / mhic1 planes (64 window samples of
+    magnitude <= 2 M through two unnormalised 8-point FFTs, squared, times
+    the kernel's constant and its 2^32 scale; the derivation is
+    oracle_lib.block_diff_sqrt_operand_bound's docstring), and that is below
+    2^96, where tests/native/sqrt_check.hip proves the root exact."""
+    F = Fixture(case)
+    cmp = gz.ButteraugliComparator(F.w, F.h, F.rgb(), F.target)
+    for tag, cand in _far_candidates(F):
+        cand = np.ascontiguousarray(cand).reshape(-1)
+        ref = oracle_compare_planes(F.w, F.h, F.rgb(), cand)
+        # (a far candidate: beyond 13.7, the farthest stage fixture)
+        assert all(np.isfinite(ref[k]).all() for k in STAGES) and ref["distance"] > 13.7, (tag, ref["distance"])
+        st = cmp.compare_stages(cand)
+        m = max(np.abs(st["mhic0"]).max(), np.abs(st["mhic1"]).max())
+        bound = block_diff_sqrt_operand_bound(m)
+        assert np.isfinite(m) and bound < SQRT_DOMAIN, "%s: max |mhic| %g, operands up to %g" % (tag, m, bound)
+        bad = ["%s: %s" % (k, mismatch(st[k], ref[k])) for k in STAGES if not bits_equal(st[k], ref[k])]
+        assert not bad, "%s, compare_stages: %s" % (tag, "; ".join(bad))
+        assert np.float32(st["distance"]) == np.float32(ref["distance"]), tag
+        pr = cmp.compare_stages_production(cand)
+        bad = ["%s: %s" % (k, mismatch(pr[k], ref[k])) for k in PROD_STAGES if not bits_equal(pr[k], ref[k])]
+        assert not bad, "%s, compare_stages_production: %s" % (tag, "; ".join(bad))
+        assert np.float32(pr["distance"]) == np.float32(ref["distance"]), tag
+        d1 = cmp.compare(cand)
+        d2 = cmp.compare(cand)  # graph replay
+        assert np.float32(d1) == np.float32(ref["distance"]) and np.float32(d2) == np.float32(ref["distance"]), (
+            tag, d1, d2, ref["distance"])
+        assert bits_equal(cmp.distmap(), ref["distmap"]), "%s, distmap(): %s" % (
+            tag, mismatch(cmp.distmap(), ref["distmap"]))
+        dm = ref["distmap"].reshape(F.h, F.w)
+        bm = np.array([max(0.0, dm[8 * by:8 * by + 8, 8 * bx:8 * bx + 8].max())
+                       for by in range(F.bh) for bx in range(F.bw)], np.float32)
+        assert bits_equal(cmp.block_max(), bm), "%s, block_max: %s" % (tag, mismatch(cmp.block_max(), bm))
+
+
+@pytest.mark.parametrize("variant", [(3, 7, 1), (2, 6, 0)])
+def test_block_zeroing_fully_dense_blocks_match_oracle(gz, variant):
+    """k_block_zeroing with every coefficient of every block non-zero: the
+    original coefficients of x_fullrange_56x41 with each zero replaced by a
+    seeded draw from {-2, -1, 1, 2}.  The DC is never a candidate
+    (ComputeBlockZeroingOrder starts at k = 1), so a block has 63 candidates
+    per searched component -- 189 with comp_mask 7, 126 with 6 -- the most the
+    sort and its stack can be given (the fixtures stop at 178, with the limit
+    cutting the emitted orders shorter); the many |coefficient| 1 and 2 tie
+    their keys.  Run at the fixture's limit (the search as the encoder runs
+    it) and at a limit no block error reaches, where every candidate is
+    emitted: that count is asserted, on the oracle's output, so the second
+    run does walk all 189 / 126 steps.  idx and block_err equal the CPU
+    oracle's (pinned on this image by test_oracle_block_zeroing_bit_exact)."""
+    import ctypes
+    L = oracle()
+    F = Fixture("x_fullrange_56x41")
+    la, mask, new_model = variant
+    n = F.w * F.h
+    rgb = F.rgb()
+    orig = F.i16("orig_coeffs.i16")
+    dense = orig.copy()
+    zeros = dense == 0
+    dense[zeros] = np.random.default_rng(7).choice(np.array([-2, -1, 1, 2], np.int16), size=int(zeros.sum()))
+    assert zeros.sum() > 1000 and np.count_nonzero(dense) == dense.size
+    xyb = np.zeros(3 * n, np.float32)
+    L.gzo_srgb_to_linear_planes(F.w, F.h, rgb, xyb)
+    L.gzo_opsin_dynamics(F.w, F.h, xyb)
+    m = np.zeros(3 * n, np.float32)
+    L.gzo_mask(F.w, F.h, xyb, xyb, m, np.zeros(3 * n, np.float32))
+    assert bits_equal(m, F.f32("ref_mask.f32"))
+    cmp = gz.ButteraugliComparator(F.w, F.h, rgb, F.target)
+    per_block = 63 * bin(mask).count("1")
+    for limit in (F.target, 1e6):
+        ref = np.zeros(F.nb * 192, COEFF_DTYPE)
+        L.gzo_block_zeroing_orders(F.w, F.h, rgb, m, dense, orig, ctypes.c_float(limit), la, mask, new_model,
+                                   ref.ctypes.data)
+        ref = ref.reshape(F.nb, 192)
+        # (unused slots are zero, and index 0 -- the Y DC -- is never emitted)
+        count = (ref["idx"] != 0).sum(axis=1)
+        if limit == 1e6:
+            assert (count == per_block).all() and ref["block_err"].max() < limit, (count.min(), count.max())
+        else:
+            assert count.max() > 70, count.max()  # (deeper than any order of the earlier fixtures)
+        out = cmp.block_zeroing_orders(dense, orig, limit, comp_mask=mask, lookahead=la,
+                                       new_zeroing_model=bool(new_model))
+        assert np.array_equal(out["idx"], ref["idx"]), "limit %g: idx differ in %d blocks" % (
+            limit, (out["idx"] != ref["idx"]).any(axis=1).sum())
+        assert bits_equal(out["block_err"], ref["block_err"]), "limit %g: %s" % (
+            limit, mismatch(out["block_err"], ref["block_err"]))

@@ -4,7 +4,11 @@ Pins the restatement before anything is checked against it: every stage of
 the `--c` Butteraugli pass, the reference-vs-reference activity mask, the
 per-block greedy zeroing orders and the libstdc++ std::sort tie order are
 compared bit-for-bit with fixtures generated from oracle/_ref (the reference
-compiled from /root/reference) by tests/golden/make_fixtures.py.
+compiled from /root/reference) by tests/golden/make_fixtures.py.  The x_*
+fixtures are extreme inputs (black, white, checkerboards, saturated
+primaries, full-range noise, ramps into 0 and 255; *_coarse: candidates a 24
+times coarser quantization away), which make the oracle the reference for
+the device tests that go farther still.
 """
 import ctypes
 import os
@@ -13,7 +17,8 @@ import subprocess
 import numpy as np
 import pytest
 
-from oracle_lib import COEFF_DTYPE, ZERO_VARIANTS, Fixture, Stages, fixture_cases, lib, ROOT
+from oracle_lib import (COEFF_DTYPE, ROOT, SQRT_DOMAIN, ZERO_VARIANTS, Fixture, Stages,
+                        block_diff_sqrt_operand_bound, fixture_cases, lib)
 
 CASES = fixture_cases()
 
@@ -83,6 +88,21 @@ def test_oracle_block_zeroing_bit_exact(case, variant):
     z = F.zero_order(None if variant == (3, 7, 1) else variant).ravel()
     assert np.array_equal(out["idx"], z["idx"])
     assert bits_equal(out["block_err"], z["block_err"])
+
+
+def test_fixture_mhic_planes_inside_sqrt_domain():
+    """k_block_diff2 takes its Y square roots with sqrt_cr_big on operands
+    scaled by 2^32, which is correctly rounded only below 2^96.  The bound of
+    those operands in terms of the largest MHIC value (oracle_lib.
+    block_diff_sqrt_operand_bound, derivation there) holds on the committed
+    mhic0 / mhic1 planes of every stage fixture: a new fixture that leaves the
+    proven range fails here, without a device."""
+    for case in CASES:
+        F = Fixture(case)
+        m = max(np.abs(F.f32("mhic0.f32")).max(), np.abs(F.f32("mhic1.f32")).max())
+        assert np.isfinite(m), case
+        bound = block_diff_sqrt_operand_bound(m)
+        assert bound < SQRT_DOMAIN, "%s: max |mhic| %g gives operands up to %g" % (case, m, bound)
 
 
 SORT_HARNESS = r"""
