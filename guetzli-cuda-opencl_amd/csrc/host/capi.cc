@@ -353,6 +353,16 @@ gz_status gz_comparator_block_zeroing_orders(gz_comparator* cmp, const int16_t* 
   return GZ_OK;
 }
 
+// The entropy coders' domain (runtime/engine.h): the host and the device
+// writer size their symbols and buffers for |stored| <= kCoeffAbsMax.
+static bool CoeffsInCoderDomain(const int16_t* coeffs, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    if (coeffs[i] > gz::kCoeffAbsMax || coeffs[i] < -gz::kCoeffAbsMax) return false;
+  return true;
+}
+static const char kCoderDomainError[] = ": a coefficient outside [-4096, 4096]";
+static_assert(gz::kCoeffAbsMax == 4096, "the message names the domain");
+
 static gz_status CopyOut(const std::string& s, uint8_t** jpeg_out, size_t* jpeg_size) {
   uint8_t* buf = static_cast<uint8_t*>(std::malloc(s.size() ? s.size() : 1));
   if (!buf) return SetError(GZ_ERR_OUT_OF_MEMORY, "out of host memory");
@@ -374,6 +384,9 @@ gz_status gz_comparator_write_jpeg(gz_comparator* cmp, const int16_t* coeffs, co
         if (q[c][k] < 1 || q[c][k] > 65535) return SetError(GZ_ERR_INVALID_ARG, "write_jpeg: quant");
       }
     gz::Engine& e = *cmp->engine;
+    // (on the host, before anything is uploaded or launched)
+    if (!CoeffsInCoderDomain(coeffs, static_cast<size_t>(3) * e.blocks() * 64))
+      return SetError(GZ_ERR_INVALID_ARG, std::string("write_jpeg") + kCoderDomainError);
     if (!e.UploadCoeffs(coeffs)) return SetError(GZ_ERR_DEVICE, "write_jpeg: " + e.error());
     gz::JpegData meta;
     std::string out, err;
@@ -390,6 +403,8 @@ gz_status gz_write_jpeg_host(int width, int height, const int16_t* coeffs, const
       return SetError(GZ_ERR_INVALID_ARG, "write_jpeg_host: bad argument");
     gz::CoeffImage img;
     img.Init(width, height);
+    if (!CoeffsInCoderDomain(coeffs, img.coeffs.size()))
+      return SetError(GZ_ERR_INVALID_ARG, std::string("write_jpeg_host") + kCoderDomainError);
     std::memcpy(img.coeffs.data(), coeffs, img.coeffs.size() * sizeof(int16_t));
     for (int c = 0; c < 3; ++c)
       for (int k = 0; k < 64; ++k) {

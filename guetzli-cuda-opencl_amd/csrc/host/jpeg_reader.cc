@@ -72,6 +72,13 @@ struct Bits {
 
 inline int Extend(int v, int s) { return s == 0 ? 0 : (v < (1 << (s - 1)) ? v - (1 << s) + 1 : v); }
 
+// The reference's limits on a decoded coefficient (DecodeDCTBlock,
+// jpeg_data_reader.cc:553-561, 589-594): a DC value that coeff_t cannot hold
+// is JPEG_NON_REPRESENTABLE_DC_COEFF, an AC symbol whose size plus the scan's
+// point transform reaches 12 bits JPEG_NON_REPRESENTABLE_AC_COEFF.
+inline bool DcFits(int v) { return v == static_cast<coeff_t>(v); }
+constexpr int kMaxAcSize = 11;
+
 struct Reader {
   const uint8_t* d;
   size_t len, pos = 0;
@@ -80,9 +87,14 @@ struct Reader {
   Huffman dc[4], ac[4];
   int restart_interval = 0;
   bool progressive = false, found_sof = false;
+  const char* why = nullptr;  // a block decoder's own reason for failing, when it has one
 
   bool Fail(const char* m) {
     if (err) *err = m;
+    return false;
+  }
+  bool Refuse(const char* m) {
+    why = m;
     return false;
   }
   bool Need(size_t k) { return pos + k <= len; }
@@ -266,6 +278,8 @@ struct Reader {
     if (progressive) {
       if (ss > se || se > 63 || (ss == 0 && se != 0) || (ss > 0 && ns != 1) || al > 13 || ah > 13)
         return Fail("bad progressive scan parameters");
+      // (the reference's ProcessScan, jpeg_data_reader.cc:811-815)
+      if (al > 10) return Fail("scan parameter Al > 10 is not supported");
     } else if (ss != 0 || se != 63 || ah != 0 || al != 0) {
       return Fail("bad sequential scan parameters");
     }
@@ -322,17 +336,18 @@ struct Reader {
             else
               ok = ah == 0 ? AcFirst(&bits, ac[ta[i]], ss, se, al, &eobrun, blk)
                            : AcRefine(&bits, ac[ta[i]], ss, se, al, &eobrun, blk);
-            if (!ok) return Fail("corrupt entropy-coded data");
+            if (!ok) return Fail(why ? why : "corrupt entropy-coded data");
           }
       }
     }
     return true;
   }
 
-  static bool Sequential(Bits* b, const Huffman& dch, const Huffman& ach, int* pred, coeff_t* blk) {
+  bool Sequential(Bits* b, const Huffman& dch, const Huffman& ach, int* pred, coeff_t* blk) {
     const int t = b->Decode(dch);
     if (t < 0 || t > 11) return false;
     *pred += Extend(t ? b->Get(t) : 0, t);
+    if (!DcFits(*pred)) return Refuse("DC coefficient not representable in 16 bits");
     blk[0] = static_cast<coeff_t>(*pred);
     for (int k = 1; k <= 63; ++k) {
       const int rs = b->Decode(ach);
@@ -345,14 +360,16 @@ struct Reader {
       }
       k += r;
       if (k > 63) return false;
+      if (s > kMaxAcSize) return Refuse("out of range AC coefficient (a symbol of 12 bits or more)");
       blk[kJPEGNaturalOrder[k]] = static_cast<coeff_t>(Extend(b->Get(s), s));
     }
     return true;
   }
-  static bool DcFirst(Bits* b, const Huffman& dch, int al, int* pred, coeff_t* blk) {
+  bool DcFirst(Bits* b, const Huffman& dch, int al, int* pred, coeff_t* blk) {
     const int t = b->Decode(dch);
     if (t < 0 || t > 11) return false;
     *pred += Extend(t ? b->Get(t) : 0, t);
+    if (!DcFits(*pred * (1 << al))) return Refuse("DC coefficient not representable in 16 bits");
     blk[0] = static_cast<coeff_t>(*pred * (1 << al));
     return true;
   }
@@ -360,7 +377,7 @@ struct Reader {
     if (b->Get(1)) blk[0] = static_cast<coeff_t>(blk[0] | (1 << al));
     return true;
   }
-  static bool AcFirst(Bits* b, const Huffman& ach, int ss, int se, int al, int* eobrun, coeff_t* blk) {
+  bool AcFirst(Bits* b, const Huffman& ach, int ss, int se, int al, int* eobrun, coeff_t* blk) {
     if (*eobrun > 0) {
       --*eobrun;
       return true;
@@ -380,6 +397,7 @@ struct Reader {
       }
       k += r;
       if (k > se) return false;
+      if (s + al > kMaxAcSize) return Refuse("out of range AC coefficient (a symbol of 12 bits or more)");
       blk[kJPEGNaturalOrder[k]] = static_cast<coeff_t>(Extend(b->Get(s), s) * (1 << al));
     }
     return true;

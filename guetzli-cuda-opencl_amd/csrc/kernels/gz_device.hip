@@ -453,8 +453,9 @@ std::unique_ptr<Engine> Engine::Create(int device, int w, int h, std::string* er
     ok = false;
   const size_t stage_groups = (3 * static_cast<size_t>(e->nb_) + kStageBlocks - 1) / kStageBlocks;
   alloc(reinterpret_cast<void**>(&e->d_jhist_), jhist_device_bytes(stage_groups));
-  // worst case per MCU: 3 x (DC 16 + 11 bits, 63 x (16 + 10) bits, EOB 16) < 160 words
-  e->jwords_cap_ = static_cast<size_t>(e->nb_) * 160 + 16;
+  // worst case per MCU of the coefficient domain (runtime/engine.h): 3 x (DC
+  // 16 + 14 bits, 63 x (16 + 13) bits) = 5571 bits <= kCodeWordsPerMcu words
+  e->jwords_cap_ = static_cast<size_t>(e->nb_) * kCodeWordsPerMcu + 16;
   alloc(reinterpret_cast<void**>(&e->d_jwords_[0]), e->jwords_cap_ * 4);
   alloc(reinterpret_cast<void**>(&e->d_jwords_[1]), e->jwords_cap_ * 4);
   const size_t code_groups = (static_cast<size_t>(e->nb_) + kCodeMcus - 1) / kCodeMcus;

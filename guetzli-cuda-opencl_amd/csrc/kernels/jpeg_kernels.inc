@@ -410,8 +410,20 @@ constexpr int kCodeMcus = 4 * kCodeMcusPerWave;  // per workgroup
 constexpr int kCodeMinBitsPerMcu = 2;
 static_assert(kCodeMcus * kCodeMinBitsPerMcu >= 32,
               "k_jpeg_code: a workgroup must span >= 32 bits so that no word is shared by three");
-// any 16 MCUs: 3 x (27 + 63 x 26) bits each < 4995
-constexpr int kCodeLdsWords = (kCodeMcus * 4995 + 31) / 32 + 2;
+// The workgroup's bits in LDS: any kCodeMcus MCUs of the coefficient domain
+// (runtime/engine.h: kCodeMaxMcuBits = 3 x (30 + 63 x 29) = 5571 each), and
+// the two words past a piece's first that lds_put_bits64 may address.
+constexpr int kCodeLdsWords = (kCodeMcus * kCodeMaxMcuBits + 31) / 32 + 2;
+static_assert(32 * (kCodeLdsWords - 2) >= kCodeMcus * kCodeMaxMcuBits,
+              "k_jpeg_code: the LDS bit buffer holds a workgroup's worst MCUs");
+// jpeg_lane_pack's fields: a magnitude length (len1) in 5 bits, a lane's
+// total (n) in 7 -- its worst is three ZRLs, a code, a DC difference and the EOB.
+static_assert(kCodeMaxDcSize < 32 && 3 * kCodeMaxCodeLen + kCodeMaxCodeLen + kCodeMaxDcSize + kCodeMaxCodeLen < 128,
+              "k_jpeg_code: jpeg_lane_pack's len1 and n fields");
+// 8 workgroups per CU (amdgpu_waves_per_eu(8, 8)) within 160 KiB of LDS:
+// the bit buffer and the code / quant tables of one workgroup
+static_assert(4 * kCodeLdsWords + 4 * (3 * 512 + 2 * 3 * 64 + kCodeMcus) + 64 <= 20480,
+              "k_jpeg_code: 8 workgroups' LDS per CU");
 constexpr uint64_t kCodeValueMask = (1ull << 48) - 1;
 constexpr int kCodeHostBits = 0, kCodeHostFirst = 2, kCodeHostLast = 3, kCodeHostFf = 8;
 constexpr int kJCodeHost = 6 * 256 + 4;  // the coder's words in the engine's mapped h_jhist_ (after the stage's)

@@ -22,6 +22,33 @@ struct CoeffDataHost {  // guetzli::CoeffData (processor.h:29-32)
   float block_err;
 };
 
+// The coefficient domain of the entropy coder, named once.  A stored
+// (dequantized) coefficient is value x quant with |stored| <= kCoeffAbsMax:
+// CheckJpegSanity's limit on a JPEG input (processor.cc:118-131, 1 << 12 at
+// every position of every block), which the coefficients of 8-bit pixels
+// stay four times below.  With a quant of 1 the coded value is the stored
+// one, and the search's re-quantization (QuantizeCoeff: the nearest multiple
+// of q) divides to at most kCoeffAbsMax / q + 1/2, so a coded AC has at most
+// kCodeMaxAcSize magnitude bits and a DC difference (of two such values) at
+// most kCodeMaxDcSize.  A Huffman code has at most kCodeMaxCodeLen bits.
+constexpr int kCoeffAbsMax = 4096;
+constexpr int kCodeMaxAcSize = 13;   // |ac| <= 4096 = 2^12: Log2Floor + 1
+constexpr int kCodeMaxDcSize = 14;   // |dc - last| <= 8192 = 2^13
+constexpr int kCodeMaxCodeLen = 16;
+static_assert((1 << (kCodeMaxAcSize - 1)) == kCoeffAbsMax && (1 << (kCodeMaxDcSize - 1)) == 2 * kCoeffAbsMax,
+              "symbol sizes of the coefficient domain");
+// Most bits one block codes to: the DC code and difference, 63 run/size
+// codes with their magnitudes (no EOB and no ZRL then: every position is
+// non-zero; a block with zeros trades each 29-bit coefficient for at most a
+// share of a 16-bit ZRL or the one 16-bit EOB), and an MCU of three blocks.
+constexpr int kCodeMaxBlockBits = (kCodeMaxCodeLen + kCodeMaxDcSize) + 63 * (kCodeMaxCodeLen + kCodeMaxAcSize);
+constexpr int kCodeMaxMcuBits = 3 * kCodeMaxBlockBits;  // 5571
+// The coder's output words per MCU (Engine::jwords_cap_ adds the words a
+// stream that starts inside a word needs).
+constexpr int kCodeWordsPerMcu = (kCodeMaxMcuBits + 31) / 32;  // 175
+static_assert(kCodeMaxMcuBits == 5571 && 32 * kCodeWordsPerMcu >= kCodeMaxMcuBits,
+              "output words per MCU cover the domain's worst MCU");
+
 // Per component Huffman code (length, code) of every symbol, as the device
 // entropy coder consumes them.
 struct JpegCodeTables {

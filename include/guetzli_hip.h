@@ -387,7 +387,19 @@ gz_status gz_comparator_compare_blocks_rgb(gz_comparator* cmp, int n, const int*
  * jpeg_data_writer.cc:540-553) of dequantized coefficients `coeffs`
  * ([3][blocks][64], multiples of quant) with quant tables `quant` ([3][64],
  * natural order), entropy coded on the comparator's device; metadata
- * stripped.  *jpeg_out is allocated by the library (gz_free). */
+ * stripped.  *jpeg_out is allocated by the library (gz_free).
+ *
+ * The coefficient domain.  A JPEG input may carry any |coefficient x quant|
+ * <= 4096 at every position (CheckJpegSanity, processor.cc:118-131) -- four
+ * times the range of the coefficients of 8-bit pixels -- and the entropy
+ * coders are sized for exactly that: AC symbols of at most 13 bits, DC
+ * differences of at most 14.  Both writer entries refuse a coefficient
+ * outside [-4096, 4096] with GZ_ERR_INVALID_ARG, on the host, before
+ * anything is uploaded or launched.  The other comparator entries (compare*,
+ * compare_blocks, block_zeroing_orders) take any int16: their integer IDCT
+ * wraps as the reference's does (idct.cc: a 32-bit sum, an int16 column
+ * pass), so they stay defined on every input; the tests pin them against
+ * that arithmetic for |coefficient| <= 4096. */
 gz_status gz_comparator_write_jpeg(gz_comparator* cmp, const int16_t* coeffs, const int* quant,
                                    uint8_t** jpeg_out, size_t* jpeg_size);
 /* The same on the host (the library's serial writer; no device needed). */

@@ -119,6 +119,8 @@ static const int kIdctM[64] = {
     -8192,  11362, -10704, 6436, 8192,  -11363, 10703, -9633, 8192,   -6437,  4433,  -2260,
 };
 
+const int* gzo_idct_matrix(void) { return kIdctM; }
+
 /* out[x] = sum_u M[8x+u] * in[u*stride], 32-bit wrap-around (idct.cc:41-137). */
 static void idct_1d(const int* in, int stride, int* out) {
   for (int x = 0; x < 8; ++x) {

@@ -46,6 +46,8 @@ void gzo_init(void);
 
 /* gamma_correct.cc:23-38 */
 double gzo_srgb8_to_linear(int v);
+/* The 64 entries of the IDCT matrix (idct.cc:29-38), M[8 * x + u]. */
+const int* gzo_idct_matrix(void);
 /* guetzli/idct.cc:139-161 */
 void gzo_block_idct(const int16_t* block, uint8_t* out);
 /* color_transform.h:211-218 */

@@ -68,6 +68,8 @@ def lib():
         L.gzo_compare_block.restype = ctypes.c_double
         L.gzo_srgb8_to_linear.argtypes = [ctypes.c_int]
         L.gzo_srgb8_to_linear.restype = ctypes.c_double
+        L.gzo_idct_matrix.argtypes = []
+        L.gzo_idct_matrix.restype = ctypes.POINTER(ctypes.c_int)
         L.gzo_init()
         _lib = L
     return _lib
@@ -215,6 +217,20 @@ def oracle_compare_planes(w, h, rgb, coeffs):
     out["distmap"] = dm
     out["distance"] = L.gzo_compare(w, h, rgb, coeffs, np.zeros(n, np.float32))
     return out
+
+
+def idct_column_wrap_share(coeffs):
+    """Share of the IDCT's column-pass outputs that leave int16, over the
+    blocks of `coeffs` (dequantized, natural order, any shape of whole
+    blocks).  ComputeBlockIDCT (idct.cc:139-149) stores (sum_u M[8 y + u] *
+    block[8 u + x] + 1024) >> 11 in a coeff_t, which wraps outside [-32768,
+    32767]; here the same sums in int64 with the oracle's copy of the matrix.
+    (For |coefficient| <= 4096 a sum is at most 8 * 11363 * 4096 < 2^29, so
+    the reference's 32-bit sum is this one.)"""
+    m = np.ctypeslib.as_array(lib().gzo_idct_matrix(), (64,)).reshape(8, 8).astype(np.int64)
+    b = np.asarray(coeffs).astype(np.int64).reshape(-1, 8, 8)  # [block][u][x]
+    col = (np.einsum("yu,bux->byx", m, b) + 1024) >> 11
+    return float(((col < -32768) | (col > 32767)).mean())
 
 
 SQRT_DOMAIN = 2.0 ** 96  # sqrt_cr_big is correctly rounded on [0, 2^96) (tests/native/sqrt_check.hip)

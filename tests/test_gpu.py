@@ -7,8 +7,11 @@ per-block greedy zeroing orders, and end-to-end JPEG bytes (sha256) of
 against the CPU oracle at sizes it finishes in seconds.  The stage fixtures
 named x_* are extreme inputs (black, white, 0/255 checkerboards, saturated
 primaries, full-range noise, ramps into 0 and 255) and their *_coarse twins
-candidates a 24 times coarser quantization away; candidates farther still
-and fully dense blocks are checked against the oracle.
+candidates a 24 times coarser quantization away; candidates farther still,
+fully dense blocks and coefficients over the whole range a JPEG input admits
+(|value| <= 4096, where the IDCT's int16 column pass wraps) are checked
+against the oracle, and the device entropy coder against the host writer on
+planes chosen for its seams, run lengths, symbol sizes and byte stuffing.
 """
 import hashlib
 import json
@@ -18,7 +21,8 @@ import numpy as np
 import pytest
 
 from oracle_lib import (COEFF_DTYPE, GOLDEN, SQRT_DOMAIN, ZERO_VARIANTS, Fixture,
-                        block_diff_sqrt_operand_bound, fixture_cases, lib as oracle, oracle_compare_planes)
+                        block_diff_sqrt_operand_bound, fixture_cases, idct_column_wrap_share, lib as oracle,
+                        oracle_compare_planes)
 
 pytestmark = pytest.mark.gpu
 
@@ -747,33 +751,17 @@ def _far_candidates(F):
     return [("zero", zero), ("noise", noise), ("negated_dc", negdc), ("drawn_dc", drawn)]
 
 
-@pytest.mark.parametrize("case", FAR_REFERENCES)
-def test_compare_far_candidates_match_oracle(gz, case):
-    """Candidates at distance 18 to 329 from a black, white, checkerboard,
-    saturated or full-range reference (the stage fixtures stop at 13.7): every
-    compare_stages plane, every plane of the search's own kernels, the
-    distance of the graph-launched pass (twice: capture and replay) and the
-    per-block maxima equal the CPU oracle's bit for bit.  The oracle is the
-    reference here -- it is pinned on the same images, fine and coarse, by
-    test_oracle_compare_stages_bit_exact.  These inputs put the clamps of
-    k_coeffs_to_srgb8, both ends of the sRGB table, interp_pair_f past its
-    table and sqrt_cr_big at exact zeros (black against flat gray: the whole
-    X plane) and at the pipeline's largest operands on the device path.
-
-    The square roots' domain, asserted: every operand k_block_diff2 hands to
-    sqrt_cr_big is at most 2 (128 M)^2 * 0.000016 * 2^32 * (1 + 2^-16), M the
-    largest |value| of the dumped mhic0 / mhic1 planes (64 window samples of
-    magnitude <= 2 M through two unnormalised 8-point FFTs, squared, times
-    the kernel's constant and its 2^32 scale; the derivation is
-    oracle_lib.block_diff_sqrt_operand_bound's docstring), and that is below
-    2^96, where tests/native/sqrt_check.hip proves the root exact."""
-    F = Fixture(case)
+def _check_candidates_against_oracle(gz, F, candidates, min_distance):
+    """Every compare_stages plane, every plane of the search's own kernels,
+    the graph-launched pass (capture and replay), distmap() and block_max()
+    of each (tag, [3][blocks][64] int16) candidate against the CPU oracle,
+    bit for bit, with the square-root operand bound asserted on the way."""
     cmp = gz.ButteraugliComparator(F.w, F.h, F.rgb(), F.target)
-    for tag, cand in _far_candidates(F):
+    for tag, cand in candidates:
         cand = np.ascontiguousarray(cand).reshape(-1)
         ref = oracle_compare_planes(F.w, F.h, F.rgb(), cand)
-        # (a far candidate: beyond 13.7, the farthest stage fixture)
-        assert all(np.isfinite(ref[k]).all() for k in STAGES) and ref["distance"] > 13.7, (tag, ref["distance"])
+        assert all(np.isfinite(ref[k]).all() for k in STAGES) and ref["distance"] > min_distance, (
+            tag, ref["distance"])
         st = cmp.compare_stages(cand)
         m = max(np.abs(st["mhic0"]).max(), np.abs(st["mhic1"]).max())
         bound = block_diff_sqrt_operand_bound(m)
@@ -795,6 +783,31 @@ def test_compare_far_candidates_match_oracle(gz, case):
         bm = np.array([max(0.0, dm[8 * by:8 * by + 8, 8 * bx:8 * bx + 8].max())
                        for by in range(F.bh) for bx in range(F.bw)], np.float32)
         assert bits_equal(cmp.block_max(), bm), "%s, block_max: %s" % (tag, mismatch(cmp.block_max(), bm))
+
+
+@pytest.mark.parametrize("case", FAR_REFERENCES)
+def test_compare_far_candidates_match_oracle(gz, case):
+    """Candidates at distance 18 to 329 from a black, white, checkerboard,
+    saturated or full-range reference (the stage fixtures stop at 13.7): every
+    compare_stages plane, every plane of the search's own kernels, the
+    distance of the graph-launched pass (twice: capture and replay) and the
+    per-block maxima equal the CPU oracle's bit for bit.  The oracle is the
+    reference here -- it is pinned on the same images, fine and coarse, by
+    test_oracle_compare_stages_bit_exact.  These inputs put the clamps of
+    k_coeffs_to_srgb8, both ends of the sRGB table, interp_pair_f past its
+    table and sqrt_cr_big at exact zeros (black against flat gray: the whole
+    X plane) and at the pipeline's largest operands on the device path.
+
+    The square roots' domain, asserted: every operand k_block_diff2 hands to
+    sqrt_cr_big is at most 2 (128 M)^2 * 0.000016 * 2^32 * (1 + 2^-16), M the
+    largest |value| of the dumped mhic0 / mhic1 planes (64 window samples of
+    magnitude <= 2 M through two unnormalised 8-point FFTs, squared, times
+    the kernel's constant and its 2^32 scale; the derivation is
+    oracle_lib.block_diff_sqrt_operand_bound's docstring), and that is below
+    2^96, where tests/native/sqrt_check.hip proves the root exact."""
+    F = Fixture(case)
+    # (a far candidate: beyond 13.7, the farthest stage fixture)
+    _check_candidates_against_oracle(gz, F, _far_candidates(F), min_distance=13.7)
 
 
 @pytest.mark.parametrize("variant", [(3, 7, 1), (2, 6, 0)])
@@ -847,3 +860,277 @@ def test_block_zeroing_fully_dense_blocks_match_oracle(gz, variant):
             limit, (out["idx"] != ref["idx"]).any(axis=1).sum())
         assert bits_equal(out["block_err"], ref["block_err"]), "limit %g: %s" % (
             limit, mismatch(out["block_err"], ref["block_err"]))
+
+
+# ---- the coefficient range a JPEG input admits: |stored| <= 4096 at every
+# position (CheckJpegSanity), four times what 8-bit pixels give.  The CPU
+# oracle is the reference: test_oracle_pixels_match_reference_on_jpeg_range
+# pins its pixels on this range against the reference decoder.
+
+JPEG_RANGE_REFERENCES = ["x_fullrange_56x41", "x_black_40x32"]
+
+
+def _jpeg_range_candidates(F):
+    """[3][blocks][64] int16 each: uniform noise over [-4096, 4096]; random
+    signs x 4096; all +4096; the original with one +-4096 outlier per block
+    and component at a seeded position."""
+    rng = np.random.default_rng(4096)
+    orig = F.i16("orig_coeffs.i16").reshape(3, F.nb, 64)
+    noise = rng.integers(-4096, 4097, size=orig.shape).astype(np.int16)
+    signs = (rng.integers(0, 2, size=orig.shape) * 8192 - 4096).astype(np.int16)
+    top = np.full_like(orig, 4096)
+    outl = orig.copy()
+    pos = rng.integers(0, 64, size=(3, F.nb))
+    sgn = (rng.integers(0, 2, size=(3, F.nb)) * 8192 - 4096).astype(np.int16)
+    np.put_along_axis(outl, pos[:, :, None], sgn[:, :, None], axis=2)
+    assert (np.abs(outl.astype(np.int32)) == 4096).sum(axis=2).min() >= 1
+    return [("noise4096", noise), ("signs4096", signs), ("all4096", top), ("outliers", outl)]
+
+
+@pytest.mark.parametrize("case", JPEG_RANGE_REFERENCES)
+def test_compare_jpeg_range_candidates_match_oracle(gz, case):
+    """Compare on candidates over the whole range JPEG input admits.  The
+    column pass of the IDCT stores int16 (k_coeffs_to_srgb8, as idct.cc's
+    colidcts): no candidate of the other tests drives a single output of that
+    pass out of int16 (test_idct_column_wrap_only_on_jpeg_range), here at
+    least 10 % (noise) and 40 % (signs) of them wrap -- asserted with the
+    same helper -- so a device IDCT that kept the pass in 32 bits differs.
+    Everything test_compare_far_candidates_match_oracle compares, against the
+    oracle, bit for bit."""
+    F = Fixture(case)
+    cands = _jpeg_range_candidates(F)
+    assert idct_column_wrap_share(cands[0][1]) >= 0.10
+    assert idct_column_wrap_share(cands[1][1]) >= 0.40
+    _check_candidates_against_oracle(gz, F, cands, min_distance=0.0)
+
+
+def test_compare_blocks_jpeg_range(gz):
+    """SwitchBlock + CompareBlock on candidate blocks over the JPEG range:
+    every block of x_fullrange_56x41 with its three component blocks drawn
+    from the noise and the sign family (seeded, per component), and once more
+    with one non-zero coefficient zeroed; gzo_compare_block's double, bit for
+    bit (as test_compare_blocks_bit_exact)."""
+    F = Fixture("x_fullrange_56x41")
+    L = oracle()
+    cmp = gz.ButteraugliComparator(F.w, F.h, F.rgb(), F.target)
+    fam = dict(_jpeg_range_candidates(F)[:2])
+    mask = F.f32("ref_mask.f32")
+    rgb = np.ascontiguousarray(F.rgb(), dtype=np.uint8).ravel()
+    rng = np.random.default_rng(29)
+    blocks, cands = [], []
+    for b in range(F.nb):
+        pick = rng.integers(0, 2, size=3)
+        blk = np.stack([(fam["noise4096"], fam["signs4096"])[pick[c]][c, b] for c in range(3)]).copy()
+        blocks += [b, b]
+        cands.append(blk.copy())
+        nz = np.flatnonzero(blk.reshape(-1))
+        blk.reshape(-1)[rng.choice(nz)] = 0
+        cands.append(blk)
+    cands = np.stack(cands).astype(np.int16)
+    err = cmp.compare_blocks(np.array(blocks), cands)
+    ref = np.array([L.gzo_compare_block(F.w, F.h, rgb, mask, b, np.ascontiguousarray(c).ravel())
+                    for b, c in zip(blocks, cands)], np.float64)
+    assert np.isfinite(ref).all()
+    bad = np.flatnonzero(err.view(np.uint64) != ref.view(np.uint64))
+    assert bad.size == 0, "%d/%d differ, e.g. block %d: %r vs %r" % (
+        bad.size, err.size, blocks[bad[0]], err[bad[0]], ref[bad[0]])
+
+
+@pytest.mark.parametrize("variant", [(3, 7, 1), (2, 6, 0)])
+def test_block_zeroing_jpeg_range_match_oracle(gz, variant):
+    """k_block_zeroing on coefficients over the JPEG range: the original and
+    the candidate are the same noise over [-4096, 4096] with a seeded half of
+    the AC positions zero (so the search zeroes values of up to 4096 one by
+    one, its incremental IDCT updates and candidate keys at their largest).
+    At the fixture's limit and at 1e6, where every non-zero AC of the
+    searched components is emitted (asserted on the oracle's output); idx and
+    block_err equal the CPU oracle's."""
+    import ctypes
+    L = oracle()
+    F = Fixture("x_fullrange_56x41")
+    la, mask, new_model = variant
+    rgb = F.rgb()
+    rng = np.random.default_rng(63)
+    orig = rng.integers(-4096, 4097, size=(3, F.nb, 64)).astype(np.int16)
+    keep = rng.random(size=orig.shape) < 0.5
+    keep[:, :, 0] = True
+    orig[~keep] = 0
+    ac_nz = (orig[:, :, 1:] != 0).sum(axis=2)  # [3][blocks]
+    assert 0.4 < (orig[:, :, 1:] != 0).mean() < 0.6
+    orig = np.ascontiguousarray(orig).reshape(-1)
+    m = F.f32("ref_mask.f32")
+    cmp = gz.ButteraugliComparator(F.w, F.h, rgb, F.target)
+    searched = sum(ac_nz[c] for c in range(3) if mask >> c & 1)
+    for limit in (F.target, 1e6):
+        ref = np.zeros(F.nb * 192, COEFF_DTYPE)
+        L.gzo_block_zeroing_orders(F.w, F.h, rgb, m, orig, orig, ctypes.c_float(limit), la, mask, new_model,
+                                   ref.ctypes.data)
+        ref = ref.reshape(F.nb, 192)
+        count = (ref["idx"] != 0).sum(axis=1)
+        if limit == 1e6:
+            assert np.array_equal(count, searched) and ref["block_err"].max() < limit, (count, searched)
+        out = cmp.block_zeroing_orders(orig, orig, limit, comp_mask=mask, lookahead=la,
+                                       new_zeroing_model=bool(new_model))
+        assert np.array_equal(out["idx"], ref["idx"]), "limit %g: idx differ in %d blocks" % (
+            limit, (out["idx"] != ref["idx"]).any(axis=1).sum())
+        assert bits_equal(out["block_err"], ref["block_err"]), "limit %g: %s" % (
+            limit, mismatch(out["block_err"], ref["block_err"]))
+
+
+def _jpeg_parts(jpeg):
+    """({(class, id): {symbol: code length}} of the file's DHT segments, the
+    entropy-coded bytes between the SOS header and EOI, stuffing included)."""
+    pos, huff = 2, {}
+    while True:
+        assert jpeg[pos] == 0xFF, pos
+        m, n = jpeg[pos + 1], 2 + int.from_bytes(jpeg[pos + 2:pos + 4], "big")
+        if m == 0xC4:
+            p = pos + 4
+            while p < pos + n:
+                tc, counts = jpeg[p], jpeg[p + 1:p + 17]
+                p += 17
+                tab = {}
+                for length, cnt in enumerate(counts, 1):
+                    for _ in range(cnt):
+                        tab[jpeg[p]] = length
+                        p += 1
+                huff[(tc >> 4, tc & 15)] = tab
+        if m == 0xDA:
+            assert jpeg[-2:] == b"\xff\xd9"
+            return huff, jpeg[pos + n:-2]
+        pos += n
+
+
+_NATURAL = np.argsort(np.array(_ZIGZAG))  # zigzag position -> natural index
+
+
+def _writer_pair(gz, cmps, w, h, co, quant, what):
+    """cmp.write_jpeg == gz.write_jpeg_host, byte for byte; returns the
+    host's file (every claim about an input is made on it)."""
+    if (w, h) not in cmps:
+        cmps[(w, h)] = gz.ButteraugliComparator(w, h, np.zeros((h, w, 3), np.uint8), 1.0)
+    co = np.ascontiguousarray(co, np.int16).reshape(-1)
+    host = gz.write_jpeg_host(co, quant, w, h)
+    dev = cmps[(w, h)].write_jpeg(co, quant)
+    assert dev == host, "%s at %dx%d: %d vs %d bytes, first difference at %d" % (
+        what, w, h, len(dev), len(host), next((i for i, (a, b) in enumerate(zip(dev, host)) if a != b), -1))
+    return host
+
+
+@pytest.mark.parametrize("family", ["minimal", "run_length", "range", "ones"])
+def test_device_jpeg_writer_adversarial_planes(gz, family):
+    """k_jpeg_code against the host writer, byte for byte, on planes chosen
+    for the coder's edges (test_device_jpeg_writer_matches_host_writer codes
+    textured images: no chosen run lengths, 0.4 % stuffed bytes, magnitudes
+    of at most 11 bits).  What each family is for is asserted on the host's
+    bytes.
+
+    minimal: all-zero planes code to 2 bits per MCU in one component
+      (kCodeMinBitsPerMcu: a workgroup of 16 MCUs spans exactly one word) --
+      8, 16, 17, 32 and 4225 blocks: a partial workgroup, one, one plus an
+      MCU, two, and 265 (past the look-back's 256-wide window); then with
+      one leading AC of every size 1..10 in block 0, so that every later
+      workgroup starts inside a word and shares both its words.
+    run_length: one non-zero AC per block at the zigzag positions around
+      every multiple of 16 (runs of 0, 14, 15, 16 = ZRL + 0, 30, 31, 32, ...,
+      61, 62), values +-1, +-1023, +-4096; and two per block separated by
+      exactly 15, 16, 31, 32, 47, 48 zeros.
+    range: noise over [-4096, 4096] and signs x 4096 at quant 1 (AC symbols
+      of 13 bits, DC differences of 14: the coefficient domain's largest),
+      quant 4, and a 16-bit table; one frame and 333 x 197.
+    ones: every AC 2^s - 1 (s seeded in 1..10), 1023 or 4095: magnitude bits
+      all ones, a stuffed ff 00 pair per >= 10 % of the scan's bytes -- the 0xff count, and
+      with it the predicted file size."""
+    cmps = {}
+    ones_q = np.ones((3, 64), np.int32)
+    if family == "minimal":
+        for w, h in [(64, 8), (128, 8), (136, 8), (256, 8), (520, 520)]:
+            nb = (w // 8) * (h // 8)
+            huff, scan = _jpeg_parts(_writer_pair(gz, cmps, w, h, np.zeros((3, nb, 64)), ones_q, "zeros"))
+            assert len(scan) == (2 * nb + 7) // 8 and set(huff) == {(0, 0), (1, 0)}, (w, h, len(scan), huff)
+        for w, h in [(136, 8), (520, 520)]:
+            nb = (w // 8) * (h // 8)
+            for s in range(1, 11):
+                for v in ((1 << s) - 1, -(1 << (s - 1))):
+                    co = np.zeros((3, nb, 64), np.int16)
+                    co[0, 0, 1] = v
+                    huff, scan = _jpeg_parts(_writer_pair(gz, cmps, w, h, co, ones_q, "leading AC %d" % v))
+                    dc, ac = huff[(0, 0)], huff[(1, 0)]
+                    lead = ac[s] + s  # run 0, size s
+                    bits = nb * (dc[0] + ac[0]) + lead
+                    assert dc[0] + ac[0] == 2 and lead % 32 != 0, (huff, s)
+                    assert len(scan.replace(b"\xff\x00", b"\xff")) == (bits + 7) // 8, (w, h, v, len(scan), bits)
+    elif family == "run_length":
+        w, h = 128, 48
+        nb = (w // 8) * (h // 8)
+        rng = np.random.default_rng(16)
+        ks = [1, 15, 16, 17, 31, 32, 33, 47, 48, 49, 62, 63]
+        vals = np.array([1, -1, 1023, -1023, 4096, -4096], np.int16)
+        co = np.zeros((3, nb, 64), np.int16)
+        for c in range(3):
+            for b in range(nb):
+                co[c, b, _NATURAL[ks[(b + 5 * c) % len(ks)]]] = rng.choice(vals)
+        huff, _ = _jpeg_parts(_writer_pair(gz, cmps, w, h, co, ones_q, "one AC per block"))
+        syms = set().union(*[set(t) for (cls, _), t in huff.items() if cls == 1])
+        # runs of k - 1 zeros: 0, 14, 15 directly, the others after one to three ZRLs; EOB unless k = 63
+        assert {0x00, 0xF0} <= syms and {0, 14, 15, 13} >= {s >> 4 for s in syms if s & 15} >= {0, 14, 15}, syms
+        assert {s & 15 for s in syms if s & 15} == {1, 10, 13}, syms
+        gaps = [15, 16, 31, 32, 47, 48]
+        co = np.zeros((3, nb, 64), np.int16)
+        for c in range(3):
+            for b in range(nb):
+                k0 = 1 + b % 3
+                co[c, b, _NATURAL[k0]] = rng.choice(vals)
+                co[c, b, _NATURAL[k0 + gaps[(b + c) % len(gaps)] + 1]] = rng.choice(vals)
+        huff, _ = _jpeg_parts(_writer_pair(gz, cmps, w, h, co, ones_q, "two ACs per block"))
+        syms = set().union(*[set(t) for (cls, _), t in huff.items() if cls == 1])
+        assert 0xF0 in syms and {s >> 4 for s in syms if s & 15} == {0, 1, 2, 15}, syms
+    elif family == "range":
+        q16 = np.random.default_rng(5).integers(1, 60001, size=(3, 64)).astype(np.int32)
+        for w, h in [(64, 48), (333, 197)]:
+            nb = ((w + 7) // 8) * ((h + 7) // 8)
+            rng = np.random.default_rng(w)
+            planes = {"noise": rng.integers(-4096, 4097, size=(3, nb, 64)).astype(np.int16),
+                      "signs": (rng.integers(0, 2, size=(3, nb, 64)) * 8192 - 4096).astype(np.int16)}
+            for tag, co in planes.items():
+                huff, _ = _jpeg_parts(_writer_pair(gz, cmps, w, h, co, ones_q, tag + " at quant 1"))
+                ac_sizes = {s & 15 for (cls, _), t in huff.items() if cls == 1 for s in t}
+                dc_sizes = {s for (cls, _), t in huff.items() if cls == 0 for s in t}
+                # (noise reaches a DC difference of +-8192 only by chance: 13 bits there)
+                assert max(ac_sizes) == 13 and max(dc_sizes) == (14 if tag == "signs" else 13), (tag, huff)
+                _writer_pair(gz, cmps, w, h, co, np.full((3, 64), 4, np.int32), tag + " at quant 4")
+                host = _writer_pair(gz, cmps, w, h, co, q16, tag + " under a 16-bit table")
+                ac_sizes = {s & 15 for (cls, _), t in _jpeg_parts(host)[0].items() if cls == 1 for s in t}
+                assert q16.max() > 255 and max(ac_sizes) <= 8, ac_sizes
+    else:
+        w, h = 128, 48
+        nb = (w // 8) * (h // 8)
+        s = np.random.default_rng(255).integers(1, 11, size=(3, nb, 64))
+        for tag, co in [("2^s - 1", (1 << s) - 1), ("1023", np.full(s.shape, 1023)), ("4095", np.full(s.shape, 4095))]:
+            co = co.astype(np.int16)
+            co[:, :, 0] = 0
+            _, scan = _jpeg_parts(_writer_pair(gz, cmps, w, h, co, ones_q, "every AC " + tag))
+            stuffed = scan.count(b"\xff\x00")
+            share = stuffed / len(scan)
+            print("stuffed share, every AC %s: %.3f" % (tag, share))
+            assert share >= 0.10, (tag, share)
+
+
+def test_device_jpeg_writer_refuses_coefficients_outside_the_coder_domain(gz):
+    """gz_comparator_write_jpeg takes |stored| <= 4096 (what the coder's LDS
+    and output budgets are derived for, runtime/engine.h): one coefficient
+    past it is INVALID_ARG with the domain in the message, on the host --
+    nothing is uploaded or launched -- and the comparator codes the next
+    plane as before."""
+    w, h = 64, 48
+    cmps = {}
+    co = np.zeros((3, 48, 64), np.int16)
+    co[1, 7, 9] = -4096
+    _writer_pair(gz, cmps, w, h, co, np.ones((3, 64), np.int32), "at the domain's edge")
+    for pos, v in [((0, 0, 0), 4097), ((1, 7, 9), -4097), ((2, 47, 63), 32767)]:
+        bad = co.copy()
+        bad[pos] = v
+        with pytest.raises(gz.GuetzliError) as ei:
+            cmps[(w, h)].write_jpeg(bad, np.ones((3, 64), np.int32))
+        assert ei.value.status == gz.GZ_ERR_INVALID_ARG and "outside [-4096, 4096]" in str(ei.value), (pos, v)
+    _writer_pair(gz, cmps, w, h, co, np.ones((3, 64), np.int32), "after a refusal")

@@ -7,11 +7,19 @@ CPU against the reference's own answers on the committed inputs
 optimized-Huffman with restart markers, progressive, 4:2:0, a guetzli
 output): sha256 of the quantized coefficients and of the decoded RGB.  The
 encode itself runs on the GPU and must reproduce the reference's bytes.
+
+The crafted_* inputs carry coefficients no 8-bit image gives: dense values at
+CheckJpegSanity's limit (|value x quant| <= 4096, four times the range of
+pixel-derived coefficients), which the reference reads and encodes, and files
+just past the reader's limits (an AC or DC symbol of 12 bits, a DC that
+coeff_t cannot hold) or the sanity check's, which it refuses -- each at the
+stage the manifest records (no rgb_sha256: the reference's decode failed).
 """
 import hashlib
 import json
 import os
 
+import numpy as np
 import pytest
 
 import guetzli_amd as gz
@@ -28,7 +36,32 @@ def _sha(b):
     return hashlib.sha256(b).hexdigest()
 
 
-@pytest.mark.parametrize("name", sorted(CASES))
+CRAFTED_OK = ["crafted_2047_q1", "crafted_2047_q2", "crafted_bees_outliers", "crafted_noise4096_q4",
+              "crafted_pm4096_q4"]
+# name -> whether the reference's decode takes the file (its encode never does)
+CRAFTED_REFUSED = {"crafted_ac_size12": False, "crafted_dc_size12": False, "crafted_dc_overflow": False,
+                   "crafted_prog_ac_al10": False, "crafted_prog_dc_al11": False, "crafted_sanity_4100": True}
+
+
+def test_crafted_known_answers_present():
+    """The crafted inputs are in the manifest with the reference's verdicts:
+    bytes and iteration count where it encodes, and for a refused file
+    whether its decode still succeeded."""
+    for name in CRAFTED_OK:
+        e = CASES[name]
+        assert e["reference_ok"] and e["iters"] >= 1 and e["bytes"] > 0 and len(e["sha256"]) == 64, name
+        assert len(e["rgb_sha256"]) == 64 and len(e["coeffs_sha256"]) == 64, name
+        assert os.path.exists(os.path.join(GOLDEN, e["input"])), name
+    for name, decodes in CRAFTED_REFUSED.items():
+        e = CASES[name]
+        assert not e["reference_ok"] and "sha256" not in e, name
+        assert ("rgb_sha256" in e) == decodes, name
+        assert os.path.exists(os.path.join(GOLDEN, e["input"])), name
+    assert sorted(n for n in CASES if n.startswith("crafted_")) == sorted(CRAFTED_OK + list(CRAFTED_REFUSED))
+
+
+# (every input the reference's decode takes; the others: test_crafted_refused_*)
+@pytest.mark.parametrize("name", sorted(n for n in CASES if "coeffs_sha256" in CASES[n]))
 def test_read_and_decode_match_reference(name):
     e = CASES[name]
     data = _data(name)
@@ -59,6 +92,70 @@ def test_reader_rejects_invalid_input(bad):
     with pytest.raises(gz.GuetzliError) as ei:
         gz.jpeg_decode(bad)
     assert ei.value.status == 1  # GZ_ERR_INVALID_ARG
+
+
+@pytest.mark.parametrize("name", sorted(CRAFTED_REFUSED))
+def test_crafted_refused_at_the_reference_stage(name):
+    """A crafted file the reference refuses is refused here at the same
+    stage: where its decode fails (ReadJpeg: an AC symbol of s + Al >= 12,
+    jpeg_data_reader.cc:589, in a sequential and in a progressive first
+    scan; a DC symbol of 12; a DC coeff_t cannot hold, :556; a scan with Al
+    above 10, :811) jpeg_decode raises INVALID_ARG; where only the encode fails
+    (CheckJpegSanity) jpeg_decode returns the reference's coefficients and
+    pixels (test_read_and_decode_match_reference) and process_jpeg is refused
+    (test_process_jpeg_crafted_refused, on the GPU)."""
+    e = CASES[name]
+    assert not e["reference_ok"]
+    data = _data(name)
+    assert _sha(data) == e["input_sha256"]
+    if "rgb_sha256" in e:
+        w, h, _, coeffs, rgb = gz.jpeg_decode(data)
+        assert _sha(coeffs.tobytes()) == e["coeffs_sha256"] and _sha(rgb.tobytes()) == e["rgb_sha256"]
+    else:
+        with pytest.raises(gz.GuetzliError) as ei:
+            gz.jpeg_decode(data)
+        assert ei.value.status == gz.GZ_ERR_INVALID_ARG
+        # (the reader's reason, not a later stage's)
+        reason = {"crafted_ac_size12": "out of range AC coefficient", "crafted_dc_size12": "corrupt entropy-coded",
+                  "crafted_dc_overflow": "DC coefficient not representable",
+                  "crafted_prog_ac_al10": "out of range AC coefficient",
+                  "crafted_prog_dc_al11": "Al > 10 is not supported"}[name]
+        assert reason in str(ei.value), str(ei.value)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(CRAFTED_REFUSED))
+def test_process_jpeg_crafted_refused(name):
+    """The encode of every refused crafted file fails with INVALID_ARG, as
+    the reference's Process returns false -- the sanity-check case included,
+    which reads and decodes."""
+    with pytest.raises(gz.GuetzliError) as ei:
+        gz.process_jpeg(_data(name), gz.Params.for_quality(CASES[name]["quality"]))
+    assert ei.value.status == gz.GZ_ERR_INVALID_ARG
+
+
+def test_write_jpeg_host_refuses_coefficients_outside_the_coder_domain():
+    """gz_write_jpeg_host takes stored coefficients of |v| <= 4096 (the
+    entropy coders' domain, sized for AC symbols of 13 bits and DC differences
+    of 14): 4096 and -4096 at any position are written and read back, 4097 or
+    -4097 anywhere -- DC, AC, last block of the last component -- is
+    INVALID_ARG."""
+    w, h = 24, 16
+    q4 = np.full((3, 64), 4, np.int32)
+    co = np.zeros((3, 6, 64), np.int16)
+    co[0, 0, 0], co[1, 3, 17], co[2, 5, 63] = 4096, 4096, -4096
+    # (at quant 4 the file holds +-1024: symbols of 11 bits, which the reader takes)
+    back = gz.jpeg_decode(gz.write_jpeg_host(co, q4, w, h))[3]
+    assert np.array_equal(back.reshape(3, 6, 64) * 4, co)
+    # at quant 1 they are symbols of 13 bits: written all the same
+    assert len(gz.write_jpeg_host(co, np.ones((3, 64), np.int32), w, h)) > 0
+    for pos, v in [((0, 0, 0), 4097), ((0, 0, 0), -4097), ((1, 2, 5), 4100), ((2, 5, 63), -4097),
+                   ((2, 5, 63), 32767), ((0, 4, 1), -32768)]:
+        bad = co.copy()
+        bad[pos] = v
+        with pytest.raises(gz.GuetzliError) as ei:
+            gz.write_jpeg_host(bad, q4, w, h)
+        assert ei.value.status == gz.GZ_ERR_INVALID_ARG and "outside [-4096, 4096]" in str(ei.value), (pos, v)
 
 
 @pytest.mark.gpu

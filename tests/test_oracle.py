@@ -11,14 +11,16 @@ times coarser quantization away), which make the oracle the reference for
 the device tests that go farther still.
 """
 import ctypes
+import hashlib
+import json
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from oracle_lib import (COEFF_DTYPE, ROOT, SQRT_DOMAIN, ZERO_VARIANTS, Fixture, Stages,
-                        block_diff_sqrt_operand_bound, fixture_cases, lib)
+from oracle_lib import (COEFF_DTYPE, GOLDEN, ROOT, SQRT_DOMAIN, ZERO_VARIANTS, Fixture, Stages,
+                        block_diff_sqrt_operand_bound, fixture_cases, idct_column_wrap_share, lib)
 
 CASES = fixture_cases()
 
@@ -103,6 +105,81 @@ def test_fixture_mhic_planes_inside_sqrt_domain():
         assert np.isfinite(m), case
         bound = block_diff_sqrt_operand_bound(m)
         assert bound < SQRT_DOMAIN, "%s: max |mhic| %g gives operands up to %g" % (case, m, bound)
+
+
+JPEG_CASES = json.load(open(os.path.join(GOLDEN, "manifest.json")))["jpeg"]
+CRAFTED_OK = sorted(n for n in JPEG_CASES if n.startswith("crafted_") and JPEG_CASES[n]["reference_ok"])
+
+
+def _crafted_dequantized(name):
+    """(w, h, [3][blocks][64] dequantized coefficients) of a crafted 4:4:4
+    input: gz.jpeg_decode's quantized values times the file's (uniform or
+    per-position) tables, which the generator's stored values were divided by."""
+    import guetzli_amd as gz
+    data = open(os.path.join(GOLDEN, JPEG_CASES[name]["input"]), "rb").read()
+    w, h, nc, co, _ = gz.jpeg_decode(data)
+    assert nc == 3
+    # the file's tables, in order of appearance: 8-bit DQT segments, zigzag order
+    tables, pos = [], 2
+    while data[pos + 1] != 0xDA:
+        n = 2 + ((data[pos + 2] << 8) | data[pos + 3])
+        if data[pos + 1] == 0xDB:
+            p = pos + 4
+            while p < pos + n:
+                assert data[p] >> 4 == 0
+                tables.append(np.frombuffer(data[p + 1:p + 65], np.uint8).astype(np.int32))
+                p += 65
+        pos += n
+    assert tables and all((t == tables[0]).all() for t in tables), "one table for all components"
+    zz = np.zeros(64, np.int32)
+    for z, nat in enumerate(_NATURAL_ORDER):
+        zz[nat] = tables[0][z]
+    return w, h, (co.reshape(3, -1, 64).astype(np.int32) * zz).astype(np.int16)
+
+
+# zigzag position -> natural index (T.81 figure A.6)
+_NATURAL_ORDER = [0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48,
+                  41, 34, 27, 20, 13, 6, 7, 14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                  30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63]
+
+
+@pytest.mark.parametrize("name", CRAFTED_OK)
+def test_oracle_pixels_match_reference_on_jpeg_range(name):
+    """gzo_coeffs_to_srgb on coefficients up to +-4096 at every position --
+    where the IDCT's int16 column pass wraps on up to half its outputs --
+    equals the reference decoder's RGB (DecodeJpegToRGB, the manifest's
+    rgb_sha256) byte for byte.  This makes the oracle the reference of the
+    device tests on that range (test_gpu.py, *_jpeg_range_*)."""
+    w, h, deq = _crafted_dequantized(name)
+    assert np.abs(deq.astype(np.int32)).max() <= 4096
+    srgb = np.zeros(3 * w * h, np.uint8)
+    lib().gzo_coeffs_to_srgb(w, h, np.ascontiguousarray(deq).ravel(), srgb)
+    assert hashlib.sha256(srgb.tobytes()).hexdigest() == JPEG_CASES[name]["rgb_sha256"]
+
+
+def test_idct_column_wrap_only_on_jpeg_range():
+    """The gap the crafted inputs close, stated on the data: the column pass
+    of the IDCT keeps its outputs in int16 (coeff_t colidcts, idct.cc:140-148),
+    and no candidate of any stage fixture -- all of them quantized transforms
+    of 8-bit pixels -- has a single output outside int16, so an IDCT that kept
+    that pass in 32 bits would pass every stage test.  On the crafted inputs
+    at least 40 % (random signs x 4096; measured 51 %) and 10 % (noise to
+    +-4096; measured 23 %) of the outputs wrap."""
+    # the helper on blocks worked by hand: a DC of 4096 gives 8192 * 4096 >> 11 =
+    # 16384 at all 64 outputs; +4096 at every u of column x = 0 gives 2 * (the
+    # matrix's row sums) = 122426, -33390, 26480, -9316, 14308, -1396, 8306,
+    # 3654 there and 0 elsewhere: two outputs of 64 outside int16
+    one = np.zeros((8, 8), np.int16)
+    one[0, 0] = 4096
+    assert idct_column_wrap_share(one) == 0.0
+    one[:, 0] = 4096
+    assert idct_column_wrap_share(one) == 2 / 64
+    for case in CASES:
+        assert idct_column_wrap_share(Fixture(case).i16("cand_coeffs.i16")) == 0.0, case
+    shares = {n: idct_column_wrap_share(_crafted_dequantized(n)[2]) for n in CRAFTED_OK}
+    print("column-pass wrap shares:", {k: round(v, 4) for k, v in shares.items()})
+    assert shares["crafted_pm4096_q4"] >= 0.40
+    assert shares["crafted_noise4096_q4"] >= 0.10
 
 
 SORT_HARNESS = r"""
