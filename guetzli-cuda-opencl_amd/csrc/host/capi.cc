@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include "host/frame.h"
+#include "host/image_view.h"
 #include "host/job_queue.h"
 #include "host/jpeg_encode.h"
 #include "host/jpeg_reader.h"
@@ -697,14 +698,70 @@ gz_status gz_frame_pack(int device, const gz_frame* frame, uint8_t* rgb_out) {
   });
 }
 
+// ---- images ---------------------------------------------------------------
+namespace {
+// gz_image -> the host's view of it, or what is wrong with it.
+const char* ToImageView(const gz_image* image, gz::ImageView* v) {
+  if (!image) return "null image";
+  v->data = static_cast<const uint8_t*>(image->data);
+  v->w = image->width;
+  v->h = image->height;
+  v->channels = image->channels;
+  v->sample = image->sample;
+  v->row_stride = image->row_stride;
+  v->pixel_stride = image->pixel_stride;
+  for (int c = 0; c < 4; ++c) v->channel_offset[c] = image->channel_offset[c];
+  v->on_device = image->on_device != 0;
+  return gz::ImageError(*v);
+}
+
+// The encode behind gz_process_image and a gz_encoder image job.
+gz_status EncodeImage(int device, const gz_params* params, const gz_image* image, gz::ProcessResult* res) {
+  return Guard("process_image", [&]() -> gz_status {
+    if (!params) return SetError(GZ_ERR_INVALID_ARG, "process_image: bad argument");
+    gz::ImageView v;
+    if (const char* bad = ToImageView(image, &v))
+      return SetError(GZ_ERR_INVALID_ARG, std::string("process_image: ") + bad);
+    std::string err;
+    const int rc = gz::Process(device, ToProcessParams(params), v, res, &err);
+    if (rc != 0) return SetError(rc, "process_image: " + err);
+    return GZ_OK;
+  });
+}
+}  // namespace
+
+gz_status gz_process_image(int device, const gz_params* params, const gz_image* image,
+                           uint8_t** jpeg_out, size_t* jpeg_size, gz_process_stats* stats) {
+  if (!jpeg_out || !jpeg_size) return SetError(GZ_ERR_INVALID_ARG, "process_image: bad argument");
+  gz::ProcessResult res;
+  const gz_status st = EncodeImage(device, params, image, &res);
+  if (st != GZ_OK) return st;
+  return Deliver(res, jpeg_out, jpeg_size, stats);
+}
+
+gz_status gz_image_pack(int device, const gz_image* image, uint8_t* rgb_out) {
+  return Guard("image_pack", [&]() -> gz_status {
+    gz::ImageView v;
+    if (const char* bad = ToImageView(image, &v))
+      return SetError(GZ_ERR_INVALID_ARG, std::string("image_pack: ") + bad);
+    if (!rgb_out) return SetError(GZ_ERR_INVALID_ARG, "image_pack: bad argument");
+    std::string err;
+    const int rc = gz::PackImageRgb(device, v, rgb_out, &err);
+    if (rc != 0) return SetError(rc, "image_pack: " + err);
+    return GZ_OK;
+  });
+}
+
 // ---- gz_encoder -----------------------------------------------------------
 namespace {
 struct EncodeJob {
+  enum Kind { kFrame, kFile, kImage };
   gz_params params;
-  bool file = false;
-  gz_frame frame;               // !file
-  const uint8_t* data = nullptr;  // file
+  Kind kind = kFrame;
+  gz_frame frame;                 // kFrame
+  const uint8_t* data = nullptr;  // kFile
   size_t len = 0;
+  gz_image image;                 // kImage
   uint64_t tag = 0;
 };
 
@@ -728,13 +785,14 @@ struct gz_encoder {
   std::unique_ptr<Queue> queue;
 
   // A worker's job body: the one-shot entry points' encode, inside their
-  // no-exception guard (EncodeFrame / EncodeFile), the failure text taken
-  // from this worker thread's gz_last_error.
+  // no-exception guard (EncodeFrame / EncodeFile / EncodeImage), the failure
+  // text taken from this worker thread's gz_last_error.
   EncodeOutcome Run(const EncodeJob& job) const {
     EncodeOutcome out;
     out.tag = job.tag;
-    out.status = job.file ? EncodeFile(device, &job.params, job.data, job.len, &out.res)
-                          : EncodeFrame(device, &job.params, &job.frame, &out.res);
+    out.status = job.kind == EncodeJob::kFile    ? EncodeFile(device, &job.params, job.data, job.len, &out.res)
+                 : job.kind == EncodeJob::kImage ? EncodeImage(device, &job.params, &job.image, &out.res)
+                                                 : EncodeFrame(device, &job.params, &job.frame, &out.res);
     if (out.status != GZ_OK) {
       out.error = g_last_error;
       out.res = gz::ProcessResult();
@@ -805,6 +863,21 @@ gz_status gz_encoder_submit(gz_encoder* enc, const gz_params* params, const gz_f
     EncodeJob j;
     j.params = *params;
     j.frame = *frame;
+    j.image = gz_image();
+    j.tag = tag;
+    return enc->Submit(std::move(j), job);
+  });
+}
+
+gz_status gz_encoder_submit_image(gz_encoder* enc, const gz_params* params, const gz_image* image,
+                                  uint64_t tag, uint64_t* job) {
+  return Guard("encoder_submit_image", [&]() -> gz_status {
+    if (!enc || !params || !image) return SetError(GZ_ERR_INVALID_ARG, "encoder_submit_image: bad argument");
+    EncodeJob j;
+    j.params = *params;
+    j.kind = EncodeJob::kImage;
+    j.frame = gz_frame();
+    j.image = *image;
     j.tag = tag;
     return enc->Submit(std::move(j), job);
   });
@@ -816,8 +889,9 @@ gz_status gz_encoder_submit_file(gz_encoder* enc, const gz_params* params, const
     if (!enc || !params || !data) return SetError(GZ_ERR_INVALID_ARG, "encoder_submit_file: bad argument");
     EncodeJob j;
     j.params = *params;
-    j.file = true;
+    j.kind = EncodeJob::kFile;
     j.frame = gz_frame();
+    j.image = gz_image();
     j.data = data;
     j.len = len;
     j.tag = tag;

@@ -68,6 +68,22 @@ std::unique_ptr<HipButteraugliComparator> HipButteraugliComparator::Create(int d
   return c;
 }
 
+std::unique_ptr<HipButteraugliComparator> HipButteraugliComparator::Create(int device, const ImageView& image,
+                                                                           float target, std::string* err) {
+  std::unique_ptr<HipButteraugliComparator> c(new HipButteraugliComparator);
+  c->engine_ = AcquireEngine(device, image.w, image.h, err);
+  if (!c->engine_) return nullptr;
+  if (!c->engine_->SetReferenceImage(image)) {
+    if (err) *err = c->engine_->error();
+    return nullptr;
+  }
+  c->w_ = image.w;
+  c->h_ = image.h;
+  c->target_ = target;
+  c->block_max_.assign(c->engine_->blocks(), 0.0f);
+  return c;
+}
+
 bool HipButteraugliComparator::OriginalJpegData(JpegData* jpg) {
   InitJpegDataYUV444(w_, h_, jpg);
   for (auto& q : jpg->quant)

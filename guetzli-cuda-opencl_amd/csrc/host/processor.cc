@@ -747,6 +747,17 @@ bool HostPackedFrame(int device, const FrameView& frame, std::vector<uint8_t>* r
   PackFrame(f, rgb->data());
   return true;
 }
+
+// The comparator's counters and timers of a finished search.
+void FillSearchStats(const HipButteraugliComparator& cmp, ProcessResult* result) {
+  result->compares = cmp.compares;
+  result->seconds_compare = cmp.seconds_compare;
+  result->seconds_zeroing = cmp.seconds_zeroing;
+  result->detail["compare_thread_cpu_s"] = cmp.cpu_compare;
+  result->detail["compare_wait_s"] = cmp.seconds_wait;
+  result->detail["compare_wait_cpu_s"] = cmp.cpu_wait;
+  result->detail["scan_bound_mismatches"] = cmp.scan_bound_mismatches;
+}
 }  // namespace
 
 int Process(int device, const ProcessParams& params, const uint8_t* rgb, bool device_ptr, int w,
@@ -836,15 +847,70 @@ int Process(int device, const ProcessParams& params, const FrameView& frame, Pro
   }
   result->seconds_setup = Since(t0);
   const int rc = ProcessJpegData(params, jpg, cmp.get(), result, err);
-  if (cmp) {
-    result->compares = cmp->compares;
-    result->seconds_compare = cmp->seconds_compare;
-    result->seconds_zeroing = cmp->seconds_zeroing;
-    result->detail["compare_thread_cpu_s"] = cmp->cpu_compare;
-    result->detail["compare_wait_s"] = cmp->seconds_wait;
-    result->detail["compare_wait_cpu_s"] = cmp->cpu_wait;
-    result->detail["scan_bound_mismatches"] = cmp->scan_bound_mismatches;
+  if (cmp) FillSearchStats(*cmp, result);
+  result->seconds_total = Since(t0);
+  result->detail["thread_cpu_s"] = ThreadCpu() - c0;
+  return rc;
+}
+
+int PackImageRgb(int device, const ImageView& image, uint8_t* rgb_out, std::string* err) {
+  if (const char* bad = ImageError(image)) {
+    if (err) *err = bad;
+    return GZ_ERR_INVALID_ARG;
   }
+  if (!image.on_device) {
+    PackImage(image, rgb_out);
+    return 0;
+  }
+  if (image.w >= 32 && image.h >= 32) {
+    // what an encode's comparator holds after its import
+    std::string e;
+    auto cmp = HipButteraugliComparator::Create(device, image, 1.0f, &e);
+    if (!cmp || !cmp->engine()->ReferenceRgb(rgb_out)) {
+      if (err) *err = cmp ? cmp->engine()->error() : e;
+      return GZ_ERR_DEVICE;
+    }
+    return 0;
+  }
+  return ImportImageRgb(device, image, rgb_out, err) ? 0 : GZ_ERR_DEVICE;
+}
+
+int Process(int device, const ProcessParams& params, const ImageView& image, ProcessResult* result,
+            std::string* err) {
+  const auto t0 = Clock::now();
+  const double c0 = ThreadCpu();
+  if (const char* bad = ImageError(image)) {
+    if (err) *err = bad;
+    return GZ_ERR_INVALID_ARG;
+  }
+  if (params.butteraugli_target > 2.0f) {
+    // (before any device work, as for a frame)
+    if (err) *err = "butteraugli target above 2.0 (quality below 84) is not supported";
+    return GZ_ERR_INVALID_ARG;
+  }
+  const int w = image.w, h = image.h;
+  if (!image.on_device || w < 32 || h < 32) {
+    // P on the host, then the tight-RGB encode
+    std::vector<uint8_t> rgb(static_cast<size_t>(3) * w * h);
+    const int rc = PackImageRgb(device, image, rgb.data(), err);
+    if (rc != 0) return rc;
+    const double pack = Since(t0);
+    const int rc2 = Process(device, params, rgb.data(), false, w, h, result, err);
+    result->seconds_setup += pack;
+    result->seconds_total += pack;
+    return rc2;
+  }
+  // q=1 coefficients on the device from the reference image the import left
+  JpegData jpg;
+  std::string e;
+  auto cmp = HipButteraugliComparator::Create(device, image, params.butteraugli_target, &e);
+  if (!cmp || !cmp->OriginalJpegData(&jpg)) {
+    if (err) *err = cmp ? cmp->error() : e;
+    return GZ_ERR_DEVICE;
+  }
+  result->seconds_setup = Since(t0);
+  const int rc = ProcessJpegData(params, jpg, cmp.get(), result, err);
+  FillSearchStats(*cmp, result);
   result->seconds_total = Since(t0);
   result->detail["thread_cpu_s"] = ThreadCpu() - c0;
   return rc;
@@ -897,15 +963,7 @@ int ProcessJpeg(int device, const ProcessParams& params, const uint8_t* data, si
   }
   result->seconds_setup = Since(t0);
   const int rc = ProcessJpegData(params, jpg, cmp.get(), result, err);
-  if (cmp) {
-    result->compares = cmp->compares;
-    result->seconds_compare = cmp->seconds_compare;
-    result->seconds_zeroing = cmp->seconds_zeroing;
-    result->detail["compare_thread_cpu_s"] = cmp->cpu_compare;
-    result->detail["compare_wait_s"] = cmp->seconds_wait;
-    result->detail["compare_wait_cpu_s"] = cmp->cpu_wait;
-    result->detail["scan_bound_mismatches"] = cmp->scan_bound_mismatches;
-  }
+  if (cmp) FillSearchStats(*cmp, result);
   result->seconds_total = Since(t0);
   result->detail["thread_cpu_s"] = ThreadCpu() - c0;
   return rc;

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "host/frame.h"
+#include "host/image_view.h"
 #include "host/image420.h"
 #include "host/jpeg_model.h"
 #include "host/jpeg_writer.h"
@@ -253,6 +254,10 @@ class HipButteraugliComparator : public Comparator {
   // or a pitched RGB / RGBA frame in the device's HBM (Engine::SetReferenceFrame).
   static std::unique_ptr<HipButteraugliComparator> Create(int device, const FrameView& frame, float target,
                                                           std::string* err);
+  // The same with the reference given as an image of any layout in the
+  // device's HBM (host/image_view.h, Engine::SetReferenceImage).
+  static std::unique_ptr<HipButteraugliComparator> Create(int device, const ImageView& image, float target,
+                                                          std::string* err);
   ~HipButteraugliComparator() override { ReleaseEngine(std::move(engine_)); }
   bool Compare(const CoeffImage& img) override;
   bool StartBlockComparisons() override;
@@ -407,6 +412,17 @@ int Process(int device, const ProcessParams& params, const FrameView& frame, Pro
             std::string* err);
 // P of a frame (3*w*h bytes, host), by the code the encode uses.
 int PackFrameRgb(int device, const FrameView& frame, uint8_t* rgb_out, std::string* err);
+
+// The same for an image (host/image_view.h; ImageError(image) must be
+// nullptr): the encode of its tight RGB8 image P.  A device image with both
+// sides >= 32 px is read where it lies by the engine's import kernel
+// (Engine::SetReferenceImage).  Host images are packed by PackImage, device
+// images below 32 px by the same kernel into a scratch buffer of 3*w*h bytes
+// (ImportImageRgb); both then take the tight-RGB call above.
+int Process(int device, const ProcessParams& params, const ImageView& image, ProcessResult* result,
+            std::string* err);
+// P of an image (3*w*h bytes, host), by the code the encode uses.
+int PackImageRgb(int device, const ImageView& image, uint8_t* rgb_out, std::string* err);
 
 // guetzli::Process(params, stats, jpeg_bytes, out) (processor.cc:1029-1066):
 // ReadJpeg, CheckJpegSanity, DecodeJpegToRGB as the comparator's reference,

@@ -37,6 +37,7 @@ __constant__ GzTables c_tab;
 #include "coeff_kernels.inc"
 #include "order_kernels.inc"
 #include "jpeg_kernels.inc"
+#include "image_import.inc"
 
 namespace gz {
 
@@ -704,6 +705,29 @@ bool Engine::SetReferenceFrame(const uint8_t* src_dev, int channels, size_t row_
   GZ_TIMED("ref_import", k_import_rgb8<<<dim3((w_ + 255) / 256, h_), 256, 0, s>>>(src_dev, row_stride, channels, dword,
                                                                                    w_, h_, d_rgb_, d_lin_));
   return ReferenceFromLinear();
+}
+
+bool Engine::SetReferenceImage(const ImageView& image) {
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  GZ_HIP(hipSetDevice(device_));
+  GZ_TIMED("ref_import_image", LaunchImportImage(image, d_rgb_, d_lin_, s));
+  return ReferenceFromLinear();
+}
+
+bool ImportImageRgb(int device, const ImageView& image, uint8_t* host_out, std::string* err) {
+  const size_t bytes = static_cast<size_t>(3) * image.w * image.h;
+  uint8_t* d_rgb = nullptr;
+  hipError_t e = hipSetDevice(device);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_rgb), bytes);
+  if (e == hipSuccess) {
+    LaunchImportImage(image, d_rgb, /*lin=*/nullptr, /*s=*/nullptr);
+    e = hipGetLastError();
+  }
+  // (the copy follows the kernel on the null stream and returns when done)
+  if (e == hipSuccess) e = hipMemcpy(host_out, d_rgb, bytes, hipMemcpyDeviceToHost);
+  if (d_rgb) (void)hipFree(d_rgb);
+  if (e != hipSuccess && err) *err = std::string("device image import failed: ") + hipGetErrorString(e);
+  return e == hipSuccess;
 }
 
 bool Engine::ReferenceFromLinear() {

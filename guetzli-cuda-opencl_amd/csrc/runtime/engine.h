@@ -17,6 +17,8 @@
 
 namespace gz {
 
+struct ImageView;  // host/image_view.h
+
 struct CoeffDataHost {  // guetzli::CoeffData (processor.h:29-32)
   int idx;
   float block_err;
@@ -104,6 +106,10 @@ class Engine {
   // frame in this device's HBM, rows row_stride bytes apart (host/frame.h):
   // one import kernel instead of the copy and the linear pass.
   bool SetReferenceFrame(const uint8_t* src_dev, int channels, size_t row_stride);
+  // The same from an image of any layout host/image_view.h describes, in this
+  // device's HBM (ImageError(image) == nullptr): one import kernel that reads
+  // the addressed samples where they lie (kernels/image_import.inc).
+  bool SetReferenceImage(const ImageView& image);
   // The reference image as the engine holds it (tight RGB8, 3*w*h bytes).
   bool ReferenceRgb(uint8_t* host_out);
   // q=1 coefficients of the reference ([3][blocks][64]); kept resident.
@@ -475,6 +481,11 @@ void ReleaseEngine(std::unique_ptr<Engine> e);
 // pooled; returns the bytes released.
 size_t TrimEnginePool(size_t keep_bytes);
 size_t EnginePoolIdleBytes();
+
+// P of a device image (3*w*h bytes, host) by the import kernel alone, through
+// a scratch buffer of that size: the entry for images too small for an engine
+// (ImageError(image) == nullptr, image in `device`'s HBM).
+bool ImportImageRgb(int device, const ImageView& image, uint8_t* host_out, std::string* err);
 
 // Per-launch HIP-event timing (off by default).
 void ProfileEnable(bool on);

@@ -61,6 +61,13 @@ class _Frame(ctypes.Structure):  # gz_frame
                 ("on_device", ctypes.c_int)]
 
 
+class _Image(ctypes.Structure):  # gz_image
+    _fields_ = [("data", ctypes.c_void_p), ("width", ctypes.c_int), ("height", ctypes.c_int),
+                ("channels", ctypes.c_int), ("sample", ctypes.c_int),
+                ("row_stride", ctypes.c_ssize_t), ("pixel_stride", ctypes.c_ssize_t),
+                ("channel_offset", ctypes.c_ssize_t * 4), ("on_device", ctypes.c_int)]
+
+
 class _EncoderOptions(ctypes.Structure):  # gz_encoder_options
     _fields_ = [("device", ctypes.c_int), ("max_in_flight", ctypes.c_int),
                 ("queue_capacity", ctypes.c_int)]
@@ -101,7 +108,7 @@ EXPORTED_SYMBOLS = (
     "gz_comparator_compare_blocks_rgb", "gz_rccl_unique_id", "gz_rccl_create", "gz_rccl_destroy",
     "gz_rccl_library", "gz_process_frame", "gz_frame_pack", "gz_encoder_create", "gz_encoder_submit",
     "gz_encoder_submit_file", "gz_encoder_wait", "gz_encoder_next", "gz_encode_result_free",
-    "gz_encoder_destroy",
+    "gz_encoder_destroy", "gz_process_image", "gz_image_pack", "gz_encoder_submit_image",
 )
 
 _lib = None
@@ -217,6 +224,12 @@ def lib():
                                    ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t),
                                    ctypes.POINTER(_Stats)]
     L.gz_frame_pack.argtypes = [i32, ctypes.POINTER(_Frame), vp]
+    L.gz_process_image.argtypes = [i32, ctypes.POINTER(_Params), ctypes.POINTER(_Image),
+                                   ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t),
+                                   ctypes.POINTER(_Stats)]
+    L.gz_image_pack.argtypes = [i32, ctypes.POINTER(_Image), vp]
+    L.gz_encoder_submit_image.argtypes = [vp, ctypes.POINTER(_Params), ctypes.POINTER(_Image), u64,
+                                          ctypes.POINTER(u64)]
     L.gz_encoder_create.argtypes = [ctypes.POINTER(_EncoderOptions), ctypes.POINTER(vp)]
     L.gz_encoder_submit.argtypes = [vp, ctypes.POINTER(_Params), ctypes.POINTER(_Frame), u64,
                                     ctypes.POINTER(u64)]
@@ -536,6 +549,96 @@ def frame_pack(image, device=0):
     return out
 
 
+_NATIVE = "<" if np.little_endian else ">"
+# typestr -> gz_sample (native-endian only; u1 has no byte order)
+_SAMPLES = {"|u1": 0, _NATIVE + "u1": 0, _NATIVE + "u2": 1, _NATIVE + "f2": 2, _NATIVE + "f4": 3}
+_ORDERS = {1: "L", 2: "LA", 3: "RGB", 4: "RGBA"}
+
+
+def _as_image(image, device, what, layout, order):
+    """gz_image of `image` and the object that keeps its memory alive: a numpy
+    array or an object with __cuda_array_interface__ (a torch tensor on the
+    GPU) of uint8, uint16, float16 or float32, described as it lies -- its
+    own strides, no copy, no conversion."""
+    cai = getattr(image, "__cuda_array_interface__", None)
+    if cai is not None:
+        keep, on_device = image, 1
+        typestr, shape, strides, data = cai.get("typestr"), cai["shape"], cai.get("strides"), cai["data"][0]
+    else:
+        keep, on_device = np.asarray(image), 0
+        typestr, shape, strides, data = keep.dtype.str, keep.shape, keep.strides, keep.ctypes.data
+    if typestr not in _SAMPLES:
+        raise GuetzliError(1, "%s: dtype %s is not one of native-endian uint8, uint16, float16, float32"
+                           % (what, typestr if cai is not None else "%s (%s)" % (keep.dtype, typestr)))
+    sample = _SAMPLES[typestr]
+    shape = tuple(int(v) for v in shape)
+    if strides is None:  # C-contiguous
+        strides, step = [], int(typestr[2:])
+        for n in reversed(shape):
+            strides.insert(0, step)
+            step *= n
+    strides = tuple(int(v) for v in strides)
+    if layout is None:
+        if len(shape) == 2:
+            layout = "HW"
+        elif len(shape) == 3 and shape[2] <= 4:
+            layout = "HWC"
+        elif len(shape) == 3 and shape[0] <= 4:
+            layout = "CHW"
+        else:
+            raise GuetzliError(1, "%s: cannot tell the layout of shape %r; pass layout='HWC', 'CHW' or 'HW'"
+                               % (what, shape))
+    if layout not in ("HWC", "CHW", "HW") or len(shape) != len(layout):
+        raise GuetzliError(1, "%s: layout %r does not fit shape %r" % (what, layout, shape))
+    dim = {axis: (shape[i], strides[i]) for i, axis in enumerate(layout)}
+    (h, rs), (w, ps), (c, cs) = dim["H"], dim["W"], dim.get("C", (1, 0))
+    if not 1 <= c <= 4:
+        raise GuetzliError(1, "%s: %d channels (shape %r as %s); an image has 1 to 4" % (what, c, shape, layout))
+    order = _ORDERS[c] if order is None else order
+    if len(order) != c or sorted(order) != sorted(_ORDERS[c]):
+        raise GuetzliError(1, "%s: order %r does not name the %d channels %r once each"
+                           % (what, order, c, _ORDERS[c]))
+    offsets = (ctypes.c_ssize_t * 4)(*[order.index(ch) * cs for ch in _ORDERS[c]])
+    if on_device and type(image).__module__.split(".")[0] == "torch":
+        import torch
+        if image.device.index is not None and image.device.index != device:
+            raise GuetzliError(1, "%s: the tensor is on device %d, the encode on device %d"
+                               % (what, image.device.index, device))
+        # the encode reads the pixels on streams of its own
+        torch.cuda.current_stream(image.device).synchronize()
+    return _Image(data, w, h, c, sample, rs, ps, offsets, on_device), keep
+
+
+def process_image(image, params=None, device=0, return_stats=False, *, layout=None, order=None):
+    """gz_process_image: process() of an image read where it lies -- a numpy
+    array or a tensor resident on the GPU (anything with
+    __cuda_array_interface__), uint8 / uint16 / float16 / float32, of any
+    strides.  layout: "HWC", "CHW" or "HW" (default: 2-D is HW, a last axis
+    <= 4 HWC, else a first axis <= 4 CHW); order: the channels as stored,
+    "RGB", "BGR", "RGBA", "BGRA", "ARGB", "ABGR", "L", "LA", ... (default by
+    channel count: L, LA, RGB, RGBA).  Alpha is blended on black; the 8-bit
+    image that is encoded is the one image_pack returns."""
+    L = lib()
+    im, keep = _as_image(image, device, "process_image", layout, order)
+    p = (params or Params())._c()
+    out, size, st = ctypes.c_void_p(), ctypes.c_size_t(), _Stats()
+    _check(L.gz_process_image(device, ctypes.byref(p), ctypes.byref(im), ctypes.byref(out),
+                              ctypes.byref(size), ctypes.byref(st)), "process_image")
+    del keep
+    data = _take_bytes(out, size)
+    return (data, _stats(st)) if return_stats else data
+
+
+def image_pack(image, device=0, *, layout=None, order=None):
+    """gz_image_pack: the tight RGB8 image (h, w, 3) an encode of `image` starts
+    from, produced by the code the encode uses."""
+    im, keep = _as_image(image, device, "image_pack", layout, order)
+    out = np.zeros((max(im.height, 0), max(im.width, 0), 3), dtype=np.uint8)
+    _check(lib().gz_image_pack(device, ctypes.byref(im), _ptr(out)), "image_pack")
+    del keep
+    return out
+
+
 class Job:
     """One submitted encode of an Encoder.  Holds the input's memory until
     the result has been delivered."""
@@ -574,8 +677,9 @@ class Encoder:
     """gz_encoder: keeps `in_flight` encodes running on one device and hands
     the results back; the way to the library's throughput (about 8 frames in
     flight per GPU).  submit() takes what process_frame() takes, or the bytes
-    of a PNG / JPEG file (process_file's dispatch), and blocks while
-    `queue_capacity` accepted jobs have not started."""
+    of a PNG / JPEG file (process_file's dispatch), submit_image() what
+    process_image() takes; both block while `queue_capacity` accepted jobs
+    have not started."""
 
     def __init__(self, device=0, in_flight=8, queue_capacity=0):
         import threading
@@ -632,6 +736,20 @@ class Encoder:
             fr, keep = _as_frame(image, self.device, "submit")
             st = L.gz_encoder_submit(h, ctypes.byref(p), ctypes.byref(fr), ctag, ctypes.byref(jid))
         _check(st, "submit")
+        job = Job(self, jid.value, tag, keep)
+        with self._lock:
+            self._jobs[job.id] = job
+        return job
+
+    def submit_image(self, image, params=None, tag=None, *, layout=None, order=None):
+        """submit() of what process_image() takes."""
+        L, h = lib(), self._handle()
+        p = (params or Params())._c()
+        ctag = tag if isinstance(tag, int) and 0 <= tag < 1 << 64 else 0
+        jid = ctypes.c_uint64()
+        im, keep = _as_image(image, self.device, "submit_image", layout, order)
+        _check(L.gz_encoder_submit_image(h, ctypes.byref(p), ctypes.byref(im), ctag, ctypes.byref(jid)),
+               "submit_image")
         job = Job(self, jid.value, tag, keep)
         with self._lock:
             self._jobs[job.id] = job

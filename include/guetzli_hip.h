@@ -16,7 +16,8 @@
  *    back to the CPU: without a usable HIP device they fail with
  *    GZ_ERR_DEVICE.
  *  - Images: 8-bit RGB, interleaved, row-major, no padding (3*w*h bytes);
- *    the frame entries (gz_frame) also take padded rows and RGBA.
+ *    the frame entries (gz_frame) also take padded rows and RGBA, the image
+ *    entries (gz_image) any strides, channel order and sample type.
  *  - Coefficients: int16, [3][blocks][64], natural (row-major) order inside
  *    a block, blocks row-major with ceil(w/8) blocks per row (the layout of
  *    guetzli::JPEGComponent::coeffs, guetzli/jpeg_data.h:138-204).
@@ -154,6 +155,57 @@ gz_status gz_process_frame(int device, const gz_params* params, const gz_frame* 
  * encode of `frame` uses. */
 gz_status gz_frame_pack(int device, const gz_frame* frame, uint8_t* rgb_out);
 
+/* ---- images: any strides, CHW / BGR / gray, 16-bit and float samples ---- */
+typedef enum { GZ_SAMPLE_U8 = 0, GZ_SAMPLE_U16 = 1, GZ_SAMPLE_F16 = 2, GZ_SAMPLE_F32 = 3 } gz_sample;
+
+/* An input image as the caller holds it, read where it lies.  Sample c of
+ * pixel (x, y) is at data + y*row_stride + x*pixel_stride + channel_offset[c].
+ * Strides are literal: there is no "0 means tight" here, a stride of 0 is a
+ * broadcast.  One struct describes HWC and CHW; BGR, BGRA and ARGB (the
+ * offsets); gray and gray + alpha; crops and step slices; bottom-up and
+ * mirrored rows (negative strides); gray expanded to three channels (offsets
+ * {0, 0, 0}).  The library reads the bytes of the addressed samples and no
+ * other byte.
+ *
+ * The image that is encoded is the tight RGB8 image P.  A sample s becomes
+ * 8 bits by q:
+ *   u8   s
+ *   u16  s >> 8 (what ReadPNG's STRIP_16 keeps)
+ *   f32  NaN gives 0; otherwise rint(min(max(s, 0), 1) * 255), one IEEE f32
+ *        multiply rounded to nearest with ties to even (0.5 gives 0, 1.5
+ *        gives 2); -0, negatives and -inf give 0, values >= 1 and +inf 255
+ *   f16  widened exactly to f32, then the f32 rule
+ * and then, quantised first and blended second as ReadPNG does:
+ *   3 channels  P = (q R, q G, q B)
+ *   4 channels  P[c] = (q c * q A + 128) / 255
+ *   1 channel   R = G = B = q V
+ *   2 channels  R = G = B = (q V * q A + 128) / 255 */
+typedef struct {
+  const void* data;            /* the address every offset below is relative to */
+  int width, height;
+  int channels;                /* 1: gray, 2: gray + alpha, 3: RGB, 4: RGBA */
+  int sample;                  /* gz_sample */
+  ptrdiff_t row_stride;        /* bytes from a pixel to the one below it; any sign, may be 0 */
+  ptrdiff_t pixel_stride;      /* bytes from a pixel to the one right of it; any sign, may be 0 */
+  ptrdiff_t channel_offset[4]; /* bytes from a pixel's address to its R, G, B, A sample
+                                  (gray: V, A); entries at index >= channels are ignored */
+  int on_device;               /* 0: host memory, 1: HBM of the device the call names */
+} gz_image;
+
+/* The bytes gz_process_rgb returns for P.  A device image with both sides
+ * >= 32 px is read in place by one import kernel (no repacking copy, no host
+ * round trip); a smaller device image is packed by the same kernel into
+ * 3*w*h bytes, a host image on the host.  GZ_ERR_INVALID_ARG, with the field
+ * named: a null struct or null data; sizes that are not positive or not below
+ * 65536; channels outside 1..4; sample outside the enum; data, a stride or a
+ * used offset that is not a multiple of the sample size (every sample must be
+ * naturally aligned). */
+gz_status gz_process_image(int device, const gz_params* params, const gz_image* image,
+                           uint8_t** jpeg_out, size_t* jpeg_size, gz_process_stats* stats);
+/* P itself (3*w*h bytes, host memory of the caller), produced by the code an
+ * encode of `image` uses. */
+gz_status gz_image_pack(int device, const gz_image* image, uint8_t* rgb_out);
+
 /* ---- encoder: a queue that keeps N encodes in flight ------------------- */
 /* The library's throughput needs several frames in flight on a device (about
  * 8); a gz_encoder is the worker pool and result table for that.
@@ -209,6 +261,10 @@ typedef struct {
 gz_status gz_encoder_create(const gz_encoder_options* options, gz_encoder** out);
 gz_status gz_encoder_submit(gz_encoder* enc, const gz_params* params, const gz_frame* frame,
                             uint64_t tag, uint64_t* job);
+/* The same for an image (the struct is copied at submit, its memory is
+ * borrowed until delivery); the job runs the code of gz_process_image. */
+gz_status gz_encoder_submit_image(gz_encoder* enc, const gz_params* params, const gz_image* image,
+                                  uint64_t tag, uint64_t* job);
 /* PNG or JPEG file bytes: a PNG is decoded (gz_png_decode) and encoded from
  * its RGB, anything else is taken as a JPEG file (gz_process_jpeg). */
 gz_status gz_encoder_submit_file(gz_encoder* enc, const gz_params* params, const uint8_t* data,
